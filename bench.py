@@ -6,7 +6,24 @@ One "step" = one reconstruct of the LLaMA-7B-shaped bf16 parameter buffer
 -- device-resident, through the drop-in fate_llm.algo.fedkseed codec (libfks.so).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode sequential|seed-shard]
-                  [--scaling weak|strong] [--gather]
+                  [--scaling weak|strong] [--gather] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it sets up the buffer, runs W
+warm-up steps, times K steps, writes its outputs if --dump-outputs is given and prints the
+result line (metric, value, ms_per_step, the rooflines computed from the timed steps and
+the committed counter summaries).  --full adds the legs that take runs of their own, each
+reported beside `value`, never as it (N = 1, sequential mode): the same reconstruct at
+the other weight decay (alt_weight_decay), on the torch_rocm stream (alt_stream, with its
+kernel's VALU roofline), from host memory to host memory on both streams (hd_inclusive),
+and the reference's CPU path timed on this host (cpu_baseline).
+
+--dump-outputs DIR: after the timed steps rank 0 writes DIR/params.npy, float32: the
+parameter buffer as the last timed step left it (what a caller of the reconstruct holds
+afterwards; bf16 -> float32 is exact).  A buffer of more than 2^23 elements is sampled at
+fixed positions (dump_positions: the 32 elements on either side of every tensor boundary
+and seeded uniform draws, sorted), so the file stays at 32 MiB.  Buffer, seeds and
+scalars are seeded: the same arguments give the same inputs in every run, and two builds
+can be compared output for output.
 
 --gpus N > 1 without WORLD_SIZE in the environment re-launches this script under
 torch.distributed.run with N ranks (one per GPU, 127.0.0.1) as a CHILD process, before
@@ -38,9 +55,9 @@ reference's rounding (DESIGN.md §7 gives its measured deviation).
 
 Rank 0 prints ONE JSON line: the metric, the binding roofline of the dominant kernel
 (VALU issue -- the reconstruct draws K*N normals from ~26 GB of traffic), the north
-star's HBM roofline next to it, and the reference CPU path timed on this host in the
-same run (cpu_baseline).  --selftest runs the launcher / timing / reporting logic on CPU
-ranks over gloo with a dummy step (no GPU, no codec): the CPU test of the N > 1 path.
+star's HBM roofline next to it, and with --full the legs named above.  --selftest runs
+the launcher / timing / reporting logic on CPU ranks over gloo with a dummy step (no GPU,
+no codec): the CPU test of the N > 1 path.
 """
 import argparse
 import json
@@ -304,6 +321,32 @@ def cpu_baseline(budget_s, wd):
     return out
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_ELEMS = 1 << 23  # float32: 32 MiB
+
+
+def dump_positions(lo, hi, bounds):
+    """Sorted positions in [lo, hi) that --dump-outputs writes: all of them up to
+    DUMP_MAX_ELEMS, else the 32 elements on either side of every tensor boundary in
+    ``bounds`` (where a kernel's tails and heads meet) and seeded uniform draws over the
+    range, DUMP_MAX_ELEMS positions before duplicates are dropped."""
+    if hi - lo <= DUMP_MAX_ELEMS:
+        return torch.arange(lo, hi, dtype=torch.int64)
+    edges = [torch.arange(max(lo, b - 32), min(hi, b + 32), dtype=torch.int64) for b in bounds if lo <= b <= hi]
+    edge = torch.cat(edges) if edges else torch.empty(0, dtype=torch.int64)
+    draws = torch.randint(lo, hi, (DUMP_MAX_ELEMS - edge.numel(),), generator=torch.Generator().manual_seed(20),
+                          dtype=torch.int64)
+    return torch.unique(torch.cat([edge, draws]))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each named tensor as DIR/<name>.npy, float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+
+
 # ------------------------------------------------------------------ launcher
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -357,9 +400,12 @@ def selftest(args, world, rank):
         x.mul_(1.0000001)
 
     dt = max_over_ranks(timed_steps(step, args, world, lambda: None), world, torch.device("cpu"))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"selftest": x})
     if rank == 0:
         print(json.dumps({"metric": "selftest", "value": args.steps / dt, "unit": "steps/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "selftest": True,
+                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                          "selftest": True,
                           "pid": os.getpid()}), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -436,8 +482,19 @@ def run(args, world, rank, local):
         sync()
         gather_ms = max_over_ranks(time.perf_counter() - t0, world, dev) * 1e3
 
+    if rank == 0 and args.dump_outputs:
+        # what this rank's steps wrote: the whole buffer, or its element shard of it (all
+        # of it again after --gather); before the --full legs below, which go on updating it
+        lo, hi = (0, total) if seed_shard or gather_ms is not None else shard_words[rank % nshards]
+        bounds, off = [], 0
+        for s in shapes:
+            bounds.append(off)
+            off += numel(s)
+        dump_outputs(args.dump_outputs, {"params": flat[dump_positions(lo, hi, bounds).to(dev)]})
+
+    full = args.full and world == 1 and not seed_shard
     alt = None
-    if world == 1 and not seed_shard and args.alt_wd != wd:
+    if full and args.alt_wd != wd:
         # the same reconstruct at the other weight decay (plan built by a 32-seed call first)
         alt_specs = [codec.ParamSpec(v, lr=1e-5, weight_decay=args.alt_wd) for v in views]
         codec.directional_step(alt_specs, ks[:32], kv[:32])
@@ -452,11 +509,11 @@ def run(args, world, rank, local):
     from fate_llm.algo.fedkseed import _native
     build_id = _native.build_id()
     alt_stream = None
-    if world == 1 and not seed_shard and args.alt_stream == "torch_rocm" and not rocm:
+    if full and args.alt_stream == "torch_rocm" and not rocm:
         alt_stream = alt_stream_leg(codec, views, ks, kv, wd, total, build_id, max(1, args.alt_stream_steps))
 
     hd = None
-    if world == 1 and not seed_shard and args.hd:
+    if full and args.hd:
         # PCIe-inclusive rate for both streams (reported beside value, never as it)
         host = torch.empty(total, dtype=dtype, pin_memory=True)
         host.copy_(flat)
@@ -573,7 +630,7 @@ def run(args, world, rank, local):
         out["alt_stream"] = alt_stream
     if hd is not None:
         out["hd_inclusive"] = hd
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_budget, wd)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -592,19 +649,26 @@ def main():
     ap.add_argument("--wd", type=lambda v: None if v == "none" else float(v), default=0.0,
                     help="weight decay of every tensor (default 0.0: the HF TrainingArguments default the "
                          "reference's ClientTrainer passes, fedkseed.py:140; 'none' = zo_utils.py:52)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also run the legs reported beside value: the other weight "
+                         "decay (--alt-wd), the torch_rocm stream (--alt-stream), host -> device -> host (--no-hd "
+                         "skips it) and the CPU baseline (--no-cpu-baseline skips it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/params.npy (float32): the buffer as the last timed step "
+                         "left it, at fixed seeded positions when it holds more than 2^23 elements")
     ap.add_argument("--alt-wd", type=lambda v: None if v == "none" else float(v), default=0.01,
-                    help="N = 1: one more timed reconstruct at this weight decay, reported beside value")
+                    help="--full, N = 1: one more timed reconstruct at this weight decay, reported beside value")
     ap.add_argument("--alt-stream", choices=("torch_rocm", "none"), default="torch_rocm",
-                    help="N = 1: one more timed reconstruct drawing the torch_rocm stream (a reference client "
-                         "whose model sits on the GPU), with its kernel's VALU roofline")
+                    help="--full, N = 1: one more timed reconstruct drawing the torch_rocm stream (a reference "
+                         "client whose model sits on the GPU), with its kernel's VALU roofline")
     ap.add_argument("--alt-stream-steps", type=int, default=3, help="timed steps of the torch_rocm leg (median)")
     ap.add_argument("--stream", choices=("torch_cpu", "torch_rocm"), default="torch_cpu",
                     help="the z stream `value` draws (default torch_cpu, the oracle-pinned stream; torch_rocm is the "
                          "drop-in's default on a GPU, timed beside it as alt_stream)")
     ap.add_argument("--no-hd", dest="hd", action="store_false",
-                    help="N = 1: skip the host -> device -> host legs (H2D + reconstruct + D2H, both streams)")
-    ap.add_argument("--cpu-budget", type=float, default=24.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full, N = 1: skip the host -> device -> host legs (H2D + reconstruct + D2H, both streams)")
+    ap.add_argument("--cpu-budget", type=float, default=24.0, help="--full: seconds the CPU baseline may take")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--mode", choices=("sequential", "seed-shard"), default="sequential")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="sequential mode, N > 1: strong = one buffer element-sharded over the GPUs (default, "

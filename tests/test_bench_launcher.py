@@ -2,13 +2,15 @@
 torch.distributed.run with N ranks, the ranks time a dummy step with the barrier +
 max-over-ranks protocol over gloo (`--selftest`), and rank 0 alone prints one JSON line
 reporting the world size the process group saw.  Also the CPU-baseline leg on a tiny
-budget (the reference's CPU path through oracle/torch_replica.py)."""
+budget (the reference's CPU path through oracle/torch_replica.py), and --dump-outputs:
+rank 0's float32 file after the last timed step, the same in every run, at fixed positions."""
 import json
 import os
 import subprocess
 import sys
 
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,6 +40,41 @@ def test_world_size_mismatch_fails_loudly():
     r = _run(["--gpus", "2", "--selftest"], env={"WORLD_SIZE": "1"})
     assert r.returncode != 0
     assert "WORLD_SIZE" in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_repeats(tmp_path):
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "2", "--selftest", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line, = _json_lines(r.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["selftest.npy"]  # rank 0 only
+        got.append(np.load(tmp_path / d / "selftest.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (1 << 16,)
+    want = np.float32(1.0)
+    for _ in range(1 + 3):  # warmup + steps of the dummy step
+        want = np.float32(want * np.float32(1.0000001))
+    assert np.array_equal(got[0], np.full(1 << 16, want, np.float32))
+    assert np.array_equal(got[0], got[1])
+
+
+def test_dump_positions_fixed_sorted_and_bounded():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = bench.dump_positions(5, 1000, [0, 400])
+    assert small.tolist() == list(range(5, 1000))  # a small range whole
+    lo, hi = 7, 7 + 16 * bench.DUMP_MAX_ELEMS
+    bounds = [0, lo, 10 ** 7, hi, 10 ** 9]
+    p = bench.dump_positions(lo, hi, bounds)
+    # M draws from 16 M positions: about M / 32 of them repeat an earlier one
+    assert p.dtype == torch.int64 and 0.95 * bench.DUMP_MAX_ELEMS < p.numel() <= bench.DUMP_MAX_ELEMS
+    assert int(p[0]) == lo and int(p[-1]) == hi - 1 and bool((p[1:] > p[:-1]).all())
+    near = set(range(10 ** 7 - 32, 10 ** 7 + 32))
+    assert near <= set(p[(p >= 10 ** 7 - 32) & (p < 10 ** 7 + 32)].tolist())
+    assert p.equal(bench.dump_positions(lo, hi, bounds))  # the same positions in every run
 
 
 @pytest.mark.parametrize("wd", [0.0, None])
