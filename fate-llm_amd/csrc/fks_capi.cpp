@@ -1634,6 +1634,53 @@ int fks_directional_step_shard(const fks_tensor* t, int32_t nt, const uint64_t* 
   });
 }
 
+int fks_digest(const fks_tensor* t, int32_t nt, uint64_t pos0, uint64_t* dev_out2, void* stream) {
+  return guarded([&] {
+    // flags, lr and wd play no part here: the list is checked for what the digest reads
+    if (nt < 0 || (nt > 0 && !t)) throw Error(-FKS_EINVAL, "bad tensor list");
+    if (!dev_out2 || ((uintptr_t)dev_out2 % 8) != 0) throw Error(-FKS_EINVAL, "null or misaligned digest output");
+    for (int i = 0; i < nt; i++) {
+      const fks_tensor& x = t[i];
+      if (x.numel < 0) throw Error(-FKS_EINVAL, "tensor " + std::to_string(i) + ": negative numel");
+      if (x.dtype != FKS_F32 && x.dtype != FKS_BF16 && x.dtype != FKS_F16)
+        throw Error(-FKS_EINVAL, "tensor " + std::to_string(i) + ": unsupported dtype code " + std::to_string(x.dtype));
+      if (x.numel > 0 && (!x.data || ((uintptr_t)x.data % elem_size(x.dtype)) != 0))
+        throw Error(-FKS_EINVAL, "tensor " + std::to_string(i) + ": null or misaligned data pointer");
+    }
+    hipError_t e = hipMemsetAsync(dev_out2, 0, 2 * sizeof(uint64_t), (hipStream_t)stream);
+    if (e != hipSuccess) throw Error(-FKS_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+    // the non-empty tensors in launches of kDigTensors, each adding its part to dev_out2
+    // (digests of disjoint element ranges combine by add and xor)
+    DigestArgs a{};
+    a.out = dev_out2;
+    auto flush = [&] {
+      if (a.nt == 0) return;
+      const int rc = launch_digest(a, stream);
+      if (rc) throw Error(-FKS_EHIP, std::string("fks_digest_kernel launch: ") + hipGetErrorString((hipError_t)rc));
+      a.nt = 0;
+      a.ntiles = 0;
+    };
+    uint64_t q = pos0;
+    for (int i = 0; i < nt; i++) {
+      const fks_tensor& x = t[i];
+      if (x.numel == 0) continue;
+      const int64_t es = (int64_t)elem_size(x.dtype), epv = 16 / es;
+      const int64_t to16 = (int64_t)((16 - (uintptr_t)x.data % 16) % 16) / es;
+      const int64_t nv = (x.numel - std::min(to16, x.numel)) / epv;  // whole aligned 16-byte vectors
+      DigestTensor& d = a.t[a.nt++];
+      d.ptr = (uint64_t)(uintptr_t)x.data;
+      d.numel = x.numel;
+      d.q1 = q + 1;
+      d.tile0 = a.ntiles;
+      d.dtype = x.dtype;
+      a.ntiles += std::max<int64_t>(1, (nv + kDigVecPerTile - 1) / kDigVecPerTile);
+      q += (uint64_t)x.numel;
+      if (a.nt == kDigTensors) flush();
+    }
+    flush();
+  });
+}
+
 int fks_stream_length(const fks_tensor* t, int32_t nt, int64_t* words) {
   return guarded([&] {
     validate(t, nt);

@@ -275,6 +275,33 @@ struct DeltaApplyDesc {
 };
 static_assert(sizeof(DeltaApplyDesc) == 32, "DeltaApplyDesc layout");
 
+// ---- FKSD-1 model digest (fks_digest.hip) ----
+// One non-empty tensor of a launch.  Its 16-byte aligned body is cut into tiles of
+// kDigVecPerTile 16-byte vectors (one wave-iteration each; a tensor without a whole
+// vector still has one tile, which hashes its few elements one per lane).
+struct DigestTensor {
+  uint64_t ptr;     // device address of element 0
+  int64_t numel;    // > 0
+  uint64_t q1;      // position of element 0 in the digested concatenation, plus 1 (mod 2^64)
+  int64_t tile0;    // the tensor's first tile (tiles of the launch's tensors laid end to end)
+  int32_t dtype;
+  int32_t pad;
+};
+static_assert(sizeof(DigestTensor) == 40, "DigestTensor layout");
+constexpr int kDigThreads = 256;
+constexpr int kDigUnroll = 4;                      // 16-byte loads in flight per lane
+constexpr int kDigVecPerTile = 64 * kDigUnroll;    // 4 KiB per tile
+constexpr int kDigWgPerCu = 8;                     // grid cap: workgroups per CU
+constexpr int kDigTensors = 64;                    // tensors per launch (by value in the arguments)
+struct DigestArgs {
+  DigestTensor t[kDigTensors];  // sorted by tile0
+  uint64_t* out;                // {sum, xor}, accumulated with device-scope atomics
+  int64_t ntiles;
+  int32_t nt;
+  int32_t pad;
+};
+int launch_digest(const DigestArgs& a, void* stream);
+
 // launchers (fks_device.hip); return hipError_t as int
 int launch_jump(const JumpArgs& a, int nseeds, void* stream);
 int launch_apply(int dtype, const ApplyArgs& a, void* stream);

@@ -624,6 +624,51 @@ def delta_apply(specs: Sequence[ParamSpec], delta: torch.Tensor, decays: Sequenc
         b.finish()
 
 
+# ---------------------------------------------------------------- model fingerprint (FKSD-1)
+# Every client of a round rebuilds its model from the same model_0 and the same sums, so the
+# clients' parameters must be identical -- and since FedKSeed moves no weights, nothing else
+# would compare them.  The digest (include/fks.h fks_digest has the definition) is computed
+# on the device, where the reconstruct has just written the parameters; its 16 bytes travel
+# with the client's history (payload.py) and the arbiter compares them (fedkseed.Trainer).
+DIGEST_BYTES = 16
+_U64 = (1 << 64) - 1
+
+
+def model_digest(tensors: Sequence[torch.Tensor], pos0: int = 0) -> torch.Tensor:
+    """The FKSD-1 digest of ``tensors`` laid end to end (all of them, in order), the list
+    starting at element ``pos0`` of a larger concatenation: an int64[2] tensor (sum, xor) on
+    the tensors' device, queued on the current stream -- no synchronisation (``digest_bytes``
+    reads it).  A non-contiguous tensor is hashed in row-major order from a staging copy."""
+    b = _Batch([ParamSpec(t) for t in tensors], "torch_cpu")  # draws nothing: the stream is irrelevant
+    device = b.device if b.device is not None else torch.device("cuda", torch.cuda.current_device())
+    L = N.load()
+    with torch.cuda.device(device):
+        out = torch.empty(2, dtype=torch.int64, device=device)
+        N.check(L.fks_digest(ctypes.addressof(b.arr), b.n, int(pos0) & _U64, out.data_ptr(), _stream_handle(device)))
+    return out  # the staging copies (b.copies) go back to torch's allocator in stream order; nothing is written back
+
+
+def digest_bytes(t: torch.Tensor) -> bytes:
+    """The 16 wire bytes of a ``model_digest`` result: sum, then xor, little-endian u64.
+    Synchronises (a device-to-host copy)."""
+    a = t.detach().cpu().numpy().astype("<i8", copy=False)
+    if a.shape != (2,):
+        raise ValueError("a model digest is an int64[2] tensor")
+    return a.tobytes()
+
+
+def combine_digests(digests: Sequence[bytes]) -> bytes:
+    """The digest of the union of disjoint element ranges (element shards, the chunks of a
+    chunked model; each digested with its own ``pos0``): sums add mod 2^64, xors xor."""
+    s = x = 0
+    for d in digests:
+        if len(d) != DIGEST_BYTES:
+            raise ValueError(f"a model digest is {DIGEST_BYTES} bytes, not {len(d)}")
+        s = (s + int.from_bytes(d[:8], "little")) & _U64
+        x ^= int.from_bytes(d[8:], "little")
+    return s.to_bytes(8, "little") + x.to_bytes(8, "little")
+
+
 def shard_range(specs: Sequence[ParamSpec], shard: int, nshards: int, stream_mode=None):
     """What element shard ``shard`` of ``nshards`` owns (fks_shard_census: the clipping
     fks_directional_step_shard launches with).  torch_cpu: the stream words [lo, hi); for

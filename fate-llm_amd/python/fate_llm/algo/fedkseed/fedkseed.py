@@ -21,6 +21,13 @@ history drawn from another stream than the rest of the federation's
 (``payload.StreamMismatchError``), since the reference's parties would otherwise apply
 one (seed, scalar) list along different directions without noticing.
 
+The model fingerprint is part of the round too: after its reconstruct a client launches the
+FKSD-1 digest of the model's parameters on the device (codec.model_digest: one streaming
+read, no synchronisation on the reconstruct path) and, over a ``payload.WireContext``,
+sends the 16 bytes with its history; the arbiter compares the clients' digests before it
+folds a round's histories and raises ``payload.ModelMismatchError`` when they differ --
+another model_0, stream, glibc or library build, none of which the stream tag can see.
+
 Round pipeline.  The reference rebuilds the model every round
 as ``copy.deepcopy(model_0).to(device)`` (fedkseed.py:132-133): a host copy of the
 whole buffer, then a pageable H2D copy.  The drop-in builds the device model directly:
@@ -42,7 +49,7 @@ import torch
 
 from . import codec
 from .args import KSeedTrainingArguments
-from .payload import WireContext, check_stream
+from .payload import History, WireContext, check_model_digests, check_stream
 from .pytorch_utils import get_optimizer_parameters_grouped_with_decay
 from .zo_utils import get_even_seed_probabilities, probability_from_amps, reconstruct_
 
@@ -66,6 +73,8 @@ class Trainer:
         wire = isinstance(ctx, WireContext)
         self.stream_mode = ctx.stream_mode if wire else None
         self.stream_grid = ctx.stream_grid if wire else None
+        # the FKSD-1 digest the clients of the last round agreed on (None: none declared one)
+        self.model_digest: Optional[bytes] = None
 
     @staticmethod
     def get_clients(ctx) -> list:
@@ -100,9 +109,18 @@ class Trainer:
                 client.put("train_once", (False, payload))
             if sums is None:
                 sums = {s.item(): 0.0 for s in self.seed_candidates}
+            # the round's histories first: a model mismatch is raised before any of them is
+            # folded into the history and the sums
+            hists = [client.get("direction_derivative_history") for client in clients]
+            digests = [getattr(hist, "model_digest", None) for hist in hists]
+            self.model_digest = check_model_digests(digests)
+            declared = sum(d is not None for d in digests)
+            if 0 < declared < len(digests):
+                logger.warning(f"FedKSeed arbiter: {len(digests) - declared} of {len(digests)} clients sent no model "
+                               "digest (reference parties, or clients with verify_model=False?) beside clients that "
+                               "did; their models cannot be checked")
             tagged = untagged = 0
-            for i, client in enumerate(clients):
-                hist = client.get("direction_derivative_history")
+            for i, hist in enumerate(hists):
                 stream = getattr(hist, "stream_mode", None)  # payload.History of a tagged record
                 grid = getattr(hist, "stream_grid", None)
                 check_stream(self.stream_mode, stream, f"client {i} (guest first, then hosts)", self.stream_grid, grid)
@@ -213,10 +231,14 @@ class ClientTrainer:
     ``model_0_placement`` (keyword, not in the reference): "host" (default; model_0
     stays as given, each round materialises it on the device through pinned staging),
     "pinned" (model_0's host tensors are pinned once; each round is one DMA) or
-    "device" (a device copy of model_0 is kept; each round is a device-to-device copy)."""
+    "device" (a device copy of model_0 is kept; each round is a device-to-device copy).
+
+    ``verify_model`` (keyword, not in the reference; default on): ``reconstruct`` launches
+    the FKSD-1 digest of the rebuilt model's parameters on the device, and over a
+    ``WireContext`` the history carries it to the arbiter, which compares the clients'."""
 
     def __init__(self, ctx, model, fedkseed_args, training_args, train_dataset, eval_dataset, data_collator,
-                 tokenizer, model_0_placement: str = "host"):
+                 tokenizer, model_0_placement: str = "host", verify_model: bool = True):
         self.ctx = ctx
         self.fedkseed_args = fedkseed_args
         self.training_args = training_args
@@ -232,6 +254,10 @@ class ClientTrainer:
         self._model_0_device = None
         self._pinned = False
         self._lock = threading.Lock()
+        self.verify_model = bool(verify_model)
+        self.model_digest = None    # this round's codec.model_digest result (a device tensor), set by reconstruct
+        self._digest_why = None     # why reconstruct launched none
+        self._digest_logged = None  # the last "no digest" reason logged (one line per reason)
 
     @property
     def stream_mode(self) -> str:
@@ -267,9 +293,49 @@ class ClientTrainer:
             check_stream(stream, kwargs.get("stream_mode"), "the arbiter", grid, kwargs.get("stream_grid"))
             if should_exit:
                 break
+            self.model_digest = self._digest_why = None
             history = self.train_once(kwargs["seed_candidates"], kwargs["seed_probabilities"],
                                       kwargs["direction_derivative_sum"])
-            sub_ctx.arbiter.put("direction_derivative_history", history)
+            sub_ctx.arbiter.put("direction_derivative_history", self._with_digest(history))
+
+    def _with_digest(self, history):
+        """The history as it is put: over a WireContext, a ``payload.History`` carrying the
+        digest this round's ``reconstruct`` launched (read here, after the local steps, so the
+        reconstruct path never waits for it); otherwise -- a plain context, whose arbiter
+        unpickles the dict, or no digest -- the object ``train_once`` returned."""
+        if self.model_digest is None:
+            why = self._digest_why or ("verify_model=False" if not self.verify_model else
+                                        "reconstruct / train_once replaced without calling ClientTrainer.reconstruct")
+            if why != self._digest_logged:
+                logger.info(f"FedKSeed client: no model digest sent ({why})")
+                self._digest_logged = why
+            return history
+        digest, self.model_digest = codec.digest_bytes(self.model_digest), None
+        if not isinstance(self.ctx, WireContext):
+            return history
+        out = History(history)
+        out.model_digest = digest
+        return out
+
+    def _launch_digest(self, model) -> None:
+        """Queue the FKSD-1 digest of ``model``'s parameters (trainable and frozen, tied ones
+        once, in ``named_parameters`` order) behind the reconstruct; the result stays on the
+        device until ``train`` reads it."""
+        self.model_digest = None
+        if not self.verify_model:
+            return
+        params = [p.data for _, p in model.named_parameters()]
+        if not params or any(p.device.type != "cuda" for p in params):
+            self._digest_why = "the model is not on a HIP device"
+            return
+        if len({p.device for p in params}) > 1:
+            self._digest_why = "the model's parameters sit on several devices"
+            return
+        odd = sorted({str(p.dtype) for p in params if p.dtype not in codec._DTYPES})
+        if odd:
+            self._digest_why = f"parameters of dtype {', '.join(odd)} (the digest covers f32, bf16 and f16)"
+            return
+        self.model_digest = codec.model_digest(params)
 
     def materialize(self, device=None):
         """A fresh copy of model_0 on ``device`` (the training device by default): the
@@ -297,6 +363,7 @@ class ClientTrainer:
             groups = get_optimizer_parameters_grouped_with_decay(model, self.weight_decay)
             reconstruct_(groups, list(direction_derivative_sum.keys()), list(direction_derivative_sum.values()),
                          lr=self.training_args.learning_rate, weight_decay=self.training_args.weight_decay)
+        self._launch_digest(model)
         return model
 
     def train_once(self, seed_candidates, seed_probabilities, direction_derivative_sum) -> Mapping[int, List[float]]:

@@ -50,6 +50,20 @@ declares the federation's stream into its own records, and a client rejects a
 "train_once" whose declared stream differs from its own.  Untagged records (a reference
 party) decode as before.
 
+**The model fingerprint travels with the history.**  Every client of a round rebuilds its
+model from the same ``model_0`` and the same sums, so the clients' parameters must be
+identical bit for bit -- but FedKSeed moves no weights, so nothing compares them, and the
+self-declared stream tag cannot see another ``model_0``, an older glibc behind a
+"torch_cpu_libm" label, an untagged party, another build of the kernels, or one bad
+element.  A history record can carry the 16-byte FKSD-1 digest of the model its sender
+reconstructed (``model_digest``; codec.model_digest computes it on the device, include/fks.h
+has the definition): flag bit 12, the bytes after the optional grid cap, and -- because a
+decoder that does not know the field must refuse the record for its version, not for
+"trailing bytes" -- record VERSION 2.  A record without a digest is byte for byte what
+version 1 wrote and stays version 1; the decoder reads both, and rejects any flag bit it
+does not know.  The arbiter's ``Trainer`` compares the digests before it folds a round's
+histories (``ModelMismatchError``).
+
 Host-side logic only; it touches no parameters and no device.
 """
 import struct
@@ -59,7 +73,8 @@ import numpy as np
 import torch
 
 MAGIC = b"FKSW"
-VERSION = 1
+VERSION = 1          # every record without a model digest (unchanged bytes)
+VERSION_DIGEST = 2   # a history record that carries one
 KIND_TRAIN_ONCE = 1
 KIND_HISTORY = 2
 
@@ -79,7 +94,15 @@ _F_STREAM_ROCM = 1 << 9
 _F_STREAM_GRID = 1 << 10  # a u32 grid cap follows the header (torch_rocm only)
 _F_STREAM_LIBM = 1 << 11  # torch_cpu with the libm flavour of fp32 z (codec.stream_identity)
 STREAMS = ("torch_cpu", "torch_cpu_libm", "torch_rocm")
+_F_MODEL_DIGEST = 1 << 12  # history, version 2: the 16-byte FKSD-1 model digest follows the grid cap
+DIGEST_BYTES = 16
 _GRID = struct.Struct("<I")
+_STREAM_MASK = _F_STREAM_TAGGED | _F_STREAM_ROCM | _F_STREAM_GRID | _F_STREAM_LIBM
+# the flag bits each kind of record knows; any other bit is a field this decoder cannot read
+_KNOWN_FLAGS = {
+    KIND_TRAIN_ONCE: _F_EXIT | _F_SEEDS_I64 | _F_HAS_SUMS | _F_SUM_KEYS | _F_HAS_PROBS | _STREAM_MASK,
+    KIND_HISTORY: _F_KEYS_I64 | _F_VALUES_F64 | _F_SPARSE | _STREAM_MASK | _F_MODEL_DIGEST,
+}
 
 _HEADER = struct.Struct("<4sBBHQ")  # magic, version, kind, flags, count
 _U32_MAX = 2 ** 32
@@ -93,12 +116,56 @@ class StreamMismatchError(RuntimeError):
     """Two parties of one federation draw different z streams (module docstring)."""
 
 
+class ModelMismatchError(RuntimeError):
+    """Two clients of one round reconstructed different models (module docstring)."""
+
+
 class History(dict):
     """A decoded ``direction_derivative_history``: the dict itself (equal to the
-    original), plus the ``stream_mode`` its sender declared (None if untagged)."""
+    original), plus the ``stream_mode`` its sender declared (None if untagged) and the
+    ``model_digest`` of the model it reconstructed (16 bytes; None if it sent none).  A
+    client sets ``model_digest`` on the History it puts; ``_WireParty.put`` encodes it."""
 
     stream_mode: Optional[str] = None
     stream_grid: Optional[int] = None
+    model_digest: Optional[bytes] = None
+
+
+def _digest_bytes(model_digest) -> bytes:
+    if model_digest is None:
+        return b""
+    d = bytes(model_digest)
+    if len(d) != DIGEST_BYTES:
+        raise WireFormatError(f"a model digest is {DIGEST_BYTES} bytes, not {len(d)}")
+    return d
+
+
+def describe_digest(d: bytes) -> str:
+    """sum:xor as hex, the two u64 of the digest."""
+    return f"{int.from_bytes(d[:8], 'little'):016x}:{int.from_bytes(d[8:], 'little'):016x}"
+
+
+def check_model_digests(digests: Sequence[Optional[bytes]]) -> Optional[bytes]:
+    """The arbiter's check of one round: ``digests[i]`` is what client i (guest first, then
+    hosts) declared, None if it declared nothing.  Every declared digest must equal the first
+    declared one; returns it (None when nobody declared one)."""
+    declared = [(i, bytes(d)) for i, d in enumerate(digests) if d is not None]
+    if not declared:
+        return None
+    first = declared[0][1]
+    if all(d == first for _, d in declared):
+        return first
+    groups: Dict[bytes, List[int]] = {}
+    for i, d in declared:
+        groups.setdefault(d, []).append(i)
+    parts = "; ".join(f"{describe_digest(d)}: " + ", ".join(f"client {i}" for i in idx) for d, idx in groups.items())
+    raise ModelMismatchError(
+        "the clients of this round reconstructed different models (FKSD-1 digest sum:xor, clients counted guest "
+        f"first, then hosts): {parts}.  All of them applied the same (seed, sum) list, so they differ in what they "
+        "applied it to or with: another model_0 (checkpoint, revision or dtype cast), another z stream or fp32 "
+        "flavour than the one declared, a glibc whose logf / sinf / cosf differ (a torch_cpu_libm party on a "
+        "glibc older than 2.28), or another build of the library (compare fks_build_id / fks_source_id).  This "
+        "round's histories were not folded into the sums")
 
 
 def _stream_flags(stream_mode: Optional[str], stream_grid: Optional[int] = None) -> int:
@@ -185,10 +252,16 @@ def _header(buf, kind: int) -> Tuple[memoryview, int, int]:
     if len(buf) < _HEADER.size:
         raise WireFormatError("truncated header")
     magic, version, k, flags, count = _HEADER.unpack_from(buf, 0)
-    if magic != MAGIC or version != VERSION:
+    if magic != MAGIC or version not in (VERSION, VERSION_DIGEST):
         raise WireFormatError(f"bad magic/version {magic!r}/{version}")
     if k != kind:
         raise WireFormatError(f"record kind {k}, expected {kind}")
+    if flags & ~_KNOWN_FLAGS[kind]:
+        raise WireFormatError(f"unknown flag bits {flags & ~_KNOWN_FLAGS[kind]:#x} on a record of kind {kind}")
+    # version 2 is exactly "a history that carries a model digest"
+    if (version == VERSION_DIGEST) != bool(kind == KIND_HISTORY and flags & _F_MODEL_DIGEST):
+        raise WireFormatError(f"version {version} record of kind {kind} with flags {flags:#x}: a model digest "
+                              f"(flag {_F_MODEL_DIGEST:#x}) and version {VERSION_DIGEST} go together")
     return buf, flags, count
 
 
@@ -271,14 +344,19 @@ def _values_block(flat: np.ndarray) -> Tuple[int, bytes]:
 
 
 def encode_history(history: Mapping[int, Sequence[float]], candidates: Optional[Sequence[int]] = None,
-                   stream_mode: Optional[str] = None, stream_grid: Optional[int] = None) -> bytes:
+                   stream_mode: Optional[str] = None, stream_grid: Optional[int] = None,
+                   model_digest: Optional[bytes] = None) -> bytes:
     """A client's ``direction_derivative_history`` (dict seed -> list of g values).
     ``candidates``: the round's seed candidates, known to both ends -- enables the
     sparse form when the history's keys are exactly these seeds in order.
     ``stream_mode`` / ``stream_grid``: the z stream the client drew its steps from (tags the
-    record)."""
-    sflags = _stream_flags(stream_mode, stream_grid)
-    gbytes = _grid_bytes(stream_grid)
+    record).  ``model_digest``: the 16-byte FKSD-1 digest of the model the client
+    reconstructed; a record that carries one is version 2, every other record is
+    unchanged."""
+    dbytes = _digest_bytes(model_digest)
+    version = VERSION_DIGEST if dbytes else VERSION
+    sflags = _stream_flags(stream_mode, stream_grid) | (_F_MODEL_DIGEST if dbytes else 0)
+    gbytes = _grid_bytes(stream_grid) + dbytes
     keys = [int(s) for s in history.keys()]
     counts = np.fromiter((len(v) for v in history.values()), dtype="<u4", count=len(keys))
     flat = np.fromiter((float(x) for v in history.values() for x in v), dtype="<f8",
@@ -286,19 +364,24 @@ def encode_history(history: Mapping[int, Sequence[float]], candidates: Optional[
     vflag, vbytes = _values_block(flat)
     if candidates is not None and keys == [int(c) for c in candidates]:
         nz = np.nonzero(counts)[0]
-        return (_HEADER.pack(MAGIC, VERSION, KIND_HISTORY, _F_SPARSE | vflag | sflags, len(nz)) + gbytes
+        return (_HEADER.pack(MAGIC, version, KIND_HISTORY, _F_SPARSE | vflag | sflags, len(nz)) + gbytes
                 + nz.astype("<u4").tobytes() + counts[nz].tobytes() + vbytes)
     karr, ki64 = _keys_array(keys)
     flags = (_F_KEYS_I64 if ki64 else 0) | vflag | sflags
-    return (_HEADER.pack(MAGIC, VERSION, KIND_HISTORY, flags, len(keys)) + gbytes
+    return (_HEADER.pack(MAGIC, version, KIND_HISTORY, flags, len(keys)) + gbytes
             + karr.astype("<i8" if ki64 else "<u4").tobytes() + counts.tobytes() + vbytes)
 
 
 def decode_history(buf, candidates: Optional[Sequence[int]] = None) -> Dict[int, List[float]]:
-    """Inverse of ``encode_history``; a tagged record decodes to a ``History`` carrying
-    the sender's ``stream_mode`` and ``stream_grid``."""
+    """Inverse of ``encode_history``; a tagged record, or one with a model digest, decodes
+    to a ``History`` carrying the sender's ``stream_mode``, ``stream_grid`` and
+    ``model_digest``."""
     buf, flags, n = _header(buf, KIND_HISTORY)
     grid, off = _read_grid(buf, flags, _HEADER.size)
+    digest = None
+    if flags & _F_MODEL_DIGEST:
+        d, off = _read(buf, off, "u1", DIGEST_BYTES)
+        digest = d.tobytes()
     if flags & _F_SPARSE:
         if candidates is None:
             raise WireFormatError("sparse history record needs the round's seed candidates")
@@ -312,10 +395,11 @@ def decode_history(buf, candidates: Optional[Sequence[int]] = None) -> Dict[int,
         raise WireFormatError(f"{len(buf) - off} trailing bytes")
     flat = vals.astype(np.float64).tolist()
     stream = _stream_of(flags)
-    out: Dict[int, List[float]] = {} if stream is None else History()
-    if stream is not None:
+    out: Dict[int, List[float]] = {} if stream is None and digest is None else History()
+    if isinstance(out, History):
         out.stream_mode = stream
         out.stream_grid = grid
+        out.model_digest = digest
     pos = 0
     if flags & _F_SPARSE:
         cand = [int(c) for c in candidates]
@@ -348,7 +432,8 @@ class _WireParty:
             self._state[self._role] = [int(s) for s in value[1]["seed_candidates"]]
             value = encode_train_once(value, stream, grid)
         elif key == "direction_derivative_history":
-            value = encode_history(value, self._state.get(self._role), stream, grid)
+            value = encode_history(value, self._state.get(self._role), stream, grid,
+                                   getattr(value, "model_digest", None))
         return self._party.put(key, value)
 
     def get(self, key):

@@ -275,6 +275,30 @@ int fks_delta_apply(const fks_tensor* t, int32_t nt, const float* delta, const d
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- FKSD-1: the model fingerprint ----
+ * Every client of a round rebuilds its model from the same model_0 and the same (seed, sum)
+ * list (fedkseed.py:130-141), so their parameters must be identical; no weights move, so
+ * nothing else would ever compare them.  The digest of a tensor list laid end to end (every
+ * tensor in order, empty ones included), placed at element offset pos0 of a larger
+ * concatenation: element e of tensor i has position q = pos0 + (numel of the tensors before
+ * i) + e, a u64; b = its raw bits (the 16 of a bf16 / f16 element, the 32 of an f32 one)
+ * zero-extended to 64; with all arithmetic mod 2^64
+ *     x = ((q + 1) * 0x9E3779B97F4A7C15) ^ b
+ *     z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z =  z ^ (z >> 31)
+ *     digest = (sum of z mod 2^64, xor of z)
+ * written to dev_out2[0], dev_out2[1] (DEVICE memory, 8-byte aligned), on the wire as two
+ * little-endian u64.  Both combiners are associative and commutative: the digests of disjoint
+ * element ranges (element shards, the chunks of a chunked model) combine by (add, xor) into
+ * the digest of their union.  Not cryptographic: it detects accidental divergence.
+ *
+ * The call zeroes dev_out2 in stream order, then accumulates; asynchronous like every entry
+ * point.  It reads the parameters only, takes no workspace, and ignores flags, lr and wd;
+ * data pointers need only the alignment of their element.  nt == 0 and all-empty lists give
+ * (0, 0).  dev_out2 == NULL or a bad dtype: -FKS_EINVAL. */
+int fks_digest(const fks_tensor* t, int32_t nt, uint64_t pos0, uint64_t* dev_out2, void* stream);
+
 /* Thread-local description of the last error (empty string if none). */
 const char* fks_last_error(void);
 
