@@ -37,6 +37,9 @@ constexpr int kBsFence = 8;      // slice kernel: compiler fence after every 8 s
 #ifndef FKS_BS_LAG               // slice kernel, two-slice passes: half 0 twists task n only once half 1
 #define FKS_BS_LAG 36            // has applied task n - FKS_BS_LAG (0: unbounded; must exceed 12)
 #endif
+#ifndef FKS_BS_R_VMEM            // slice kernel, wd 0 chain: of every byte column's 8 seeds, this many take R
+#define FKS_BS_R_VMEM 3          // from the device-global table through the vector-memory path, loaded ahead
+#endif                           // (0..8).  3: 2.3 % faster; 0, 1, 2, 4: no gain (profiles/r07_bs_colimit_ab.log)
 #ifndef FKS_F32_SEED_PAIRS       // fp32 19-seed kernel: seed PAIRS sharing packed float ops, this many
 #define FKS_F32_SEED_PAIRS 0     // interleaved per step (0: one seed per z computation).  Measured
 #endif                           // 7-9 % SLOWER for 1-3 (profiles/r05c_f32_seedpair_ab.log)
@@ -2149,6 +2152,17 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   uint64_t seg_ptr = 0;
   float seg_lr = 0.0f, seg_wd = 0.0f;
   bool seg_wdf = false;
+  constexpr int kEs = MODE == kModeDelta ? 4 : 2;  // bytes per parameter (the delta buffer is f32)
+  // The wd 0 chain (kInc) addresses a task without division or 64-bit compares: the segment
+  // as 32-bit word offsets into this chunk, [seg_lo, seg_hi) clamped to int (a task word
+  // offset u1 stays below 2^31), and the address of chunk word 0 in the segment's tensor, so
+  // that a lane's address is seg_org + 2 or 4 u1: one 32-bit offset added; and the state row
+  // carried from task to task (next_row()).  The other chains keep the 64-bit form: with the
+  // 32-bit one the weight-decay chain measured 0.4 % and the no-wd chain 0.6 % slower
+  // (profiles/r07_bs_colimit_ab.log, profiles/r07_bench_parent_vs_v1all.log).
+  constexpr bool kInc = MODE == kModeUpdateWd0;
+  int seg_lo = INT32_MAX, seg_hi = INT32_MAX;
+  uint64_t seg_org = 0;
   auto load_seg = [&]() {
     if (cur < a.nsegs) {
       const DevSeg sg = a.segs[cur];
@@ -2161,6 +2175,12 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     } else {
       seg_start = seg_end = INT64_MAX;
     }
+    if (kInc) {
+      const int64_t lo = seg_start - wbase, hi = seg_end - wbase;  // past the last segment: >= INT32_MAX
+      seg_lo = (int)(lo < INT32_MIN ? INT32_MIN : lo > INT32_MAX ? INT32_MAX : lo);
+      seg_hi = (int)(hi < INT32_MIN ? INT32_MIN : hi > INT32_MAX ? INT32_MAX : hi);
+      seg_org = seg_ptr - (uint64_t)lo * kEs;  // only used where seg_lo <= u1 < seg_hi
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see fks_apply_kernel
   };
   load_seg();
@@ -2170,17 +2190,23 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // the neighbour lane (swap_adjacent).  Lanes past the chunk or off every fast segment
   // read and write the sink.
   using ST = Traits<MODE == kModeDelta ? FKS_F32 : FKS_BF16>;
-  constexpr int kEs = MODE == kModeDelta ? 4 : 2;
   typedef typename ST::Pair Pair;
   struct Slot { uint64_t addr; float lr, wd; uint32_t wdf; Pair raw; };
   auto fetch = [&](int n) -> Slot {
     Slot sl;
     const int u1 = kBsTaskWords * n + toff;
-    const int64_t s1 = wbase + u1;
-    while (s1 >= seg_end) { cur++; load_seg(); }
-    const bool on = u1 < nwords && s1 >= seg_start;
-    sl.lr = seg_lr; sl.wd = seg_wd; sl.wdf = seg_wdf;
-    sl.addr = on ? seg_ptr + (uint64_t)(s1 - seg_start + (odd ? 7 : 0)) * kEs : (uint64_t)(uintptr_t)a.sink;
+    if (kInc) {
+      while (u1 >= seg_hi) { cur++; load_seg(); }
+      const bool on = u1 < nwords && u1 >= seg_lo;
+      sl.lr = seg_lr; sl.wd = seg_wd; sl.wdf = seg_wdf;
+      sl.addr = on ? seg_org + (uint64_t)(uint32_t)(u1 + (odd ? 7 : 0)) * kEs : (uint64_t)(uintptr_t)a.sink;
+    } else {
+      const int64_t s1 = wbase + u1;
+      while (s1 >= seg_end) { cur++; load_seg(); }
+      const bool on = u1 < nwords && s1 >= seg_start;
+      sl.lr = seg_lr; sl.wd = seg_wd; sl.wdf = seg_wdf;
+      sl.addr = on ? seg_ptr + (uint64_t)(s1 - seg_start + (odd ? 7 : 0)) * kEs : (uint64_t)(uintptr_t)a.sink;
+    }
     sl.raw = ST::load_pair(sl.addr);
     return sl;
   };
@@ -2191,10 +2217,20 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // any lane stores it -- through data dependence, since new plane 4q+3 needs V plane
   // 4q+4 of chunk q+1, loaded one step ahead; U31 and V plane 0 are loaded first.  M
   // rows lie 227 words back, outside the task, so the task never stores them.
+  // The state row of the lane's word toff of the wave's current task, (128 n + toff) mod 624.
+  // A wave's tasks lie kBsWaves * 128 = 768 words apart, so the row moves on by 144 mod 624:
+  // divided out once here and carried by next_row() from then on.
+  constexpr int kRowStep = kBsWaves * kBsTaskWords % kMtN;
+  int row = (kBsTaskWords * hw + toff) % kMtN;
+  auto next_row = [&]() {
+    if (!kInc) return;
+    row += kRowStep;
+    if (row >= kMtN) row -= kMtN;
+  };
   auto twist = [&](const int n, uint32_t (&oa)[8], uint32_t (&ob)[8]) {
     const int u1 = kBsTaskWords * n + toff;
     const bool valid = u1 < nwords;
-    const int i1 = valid ? u1 % kMtN : 0;
+    const int i1 = valid ? (kInc ? row : u1 % kMtN) : 0;
     const int ia = flip ? i1 + 8 : i1, ib = flip ? i1 : i1 + 8;  // first / second row
     auto rows = [&](int i, uint32_t& av, uint32_t& am, uint32_t& au) {
       const int iv = i + 1 < kMtN ? i + 1 : 0;
@@ -2257,9 +2293,38 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // ---- the 32-seed chain of the lane's two parameters (slot sl), z from the bytes of
   // twist(): z = bf16(R[a] C[b]) + 0, bf16(R[a] S[b]) + 0 (normal_fill_16<BFloat16>: an
   // exact f32 product, one rounding; the fma's +0 turns -0 into +0 like "+ mean")
-  auto chain = [&](const Slot& sl, uint32_t (&oa)[8], uint32_t (&ob)[8]) {
+  // In the wd 0 chain, with FKS_BS_R_VMEM = m > 0, the first m seeds of every byte column take
+  // R from the device-global table (c_tab_bf16, L1-resident) instead of the LDS: chain_head()
+  // issues all 4 m loads of the task, BEFORE the task's parameter prefetch and after half 0's
+  // vmcnt(0) of publish_stored().  Vector-memory loads return in order, so a column's radii
+  // never wait for the prefetch behind them, and the compiler counts every vmcnt itself (plain
+  // loads: vmcnt(4 m) down to vmcnt(1) through the chain, the prefetch last).  All at the task
+  // head rather than one column ahead: issued inside the chain they would queue behind the
+  // prefetch, whose HBM latency every column would then wait out; the price is 4 m live VGPRs
+  // (126 against 121 for m = 3, no spill).  A segment walk inside fetch() (rare) drains them
+  // early through load_seg()'s vmcnt(0), which costs time, not correctness.
+  // Only the wd 0 chain: the weight-decay chain measured 2 % and the no-wd chain 0.9 % slower
+  // with it (profiles/r07_bs_colimit_ab.log); the delta chain was not measured.
+  constexpr int kRv = kInc ? FKS_BS_R_VMEM : 0;
+  static_assert(kRv >= 0 && kRv <= 8, "FKS_BS_R_VMEM");
+  // seed k's slot in rv, or -1 where it reads the LDS
+  auto rv_slot = [](const int k) __attribute__((always_inline)) -> int {
+    return (k & 7) < kRv ? (k >> 3) * kRv + (k & 7) : -1;
+  };
+  auto chain_head = [&](uint32_t (&oa)[8], uint32_t (&ob)[8], float (&rv)[4 * kRv + 1]) {
     bs::transpose8(oa);
     bs::transpose8(ob);
+#pragma unroll
+    for (int k = 0; k < kBsSeeds; k++)
+      if (rv_slot(k) >= 0)
+        rv[rv_slot(k)] =
+            *reinterpret_cast<const float*>(reinterpret_cast<const char*>(c_tab_bf16) + bs_index<2>(oa[k & 7], k >> 3));
+  };
+  auto chain = [&](const Slot& sl, uint32_t (&oa)[8], uint32_t (&ob)[8], const float (&rv)[4 * kRv + 1]) {
+    if (kRv == 0) {
+      bs::transpose8(oa);
+      bs::transpose8(ob);
+    }
     f32x2_t p;
     {
       const uint32_t keep = odd ? ST::hi(sl.raw) : ST::lo(sl.raw);
@@ -2268,9 +2333,11 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
       p.y = ST::cvt(odd ? keep : got);
     }
     auto z_of = [&](const int k) __attribute__((always_inline)) -> f32x2_t {
-      // (R read through the vector-memory path instead, an L1-resident 1 KB table off the
-      // LDS: 13 % slower, profiles/r04rg_r_global_ab.log)
-      const float r = lds_f32(bs_index<2>(oa[k & 7], k >> 3));
+      // (all 32 R reads through the vector-memory path, each issued at its seed and waited
+      // for there: 13 % slower, profiles/r04rg_r_global_ab.log.  R as bf16, two entries per
+      // LDS dword, read by ds_read_u16_d16_hi into a zeroed register: 0.2 % slower alone, 2.6 %
+      // slower beside the vector-memory radii, profiles/r07_bs_colimit_ab.log)
+      const float r = rv_slot(k) >= 0 ? rv[rv_slot(k)] : lds_f32(bs_index<2>(oa[k & 7], k >> 3));
       const f32x2_t rr = {r, r}, zero = {0.0f, 0.0f};
       const f32x2_t cs = lds_f32x2(1024u + bs_index<3>(ob[k & 7], k >> 3));
       return rnd2<FKS_BF16>(__builtin_elementwise_fma(rr, cs, zero));
@@ -2349,11 +2416,13 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     } else if (ordered) {
       await_stored(n + kBsWaves);
     }
+    float rv[4 * kRv + 1];
+    if (kRv > 0) chain_head(oa, ob, rv);
     nx = fetch(n + kBsWaves);
 #if FKS_BS_DIAG_NOCHAIN  // diagnostic (wrong values): the twist and its hand-offs alone
-    if (__builtin_amdgcn_readfirstlane(oa[0] ^ ob[0]) == 0x12345u) chain(sl, oa, ob);
+    if (__builtin_amdgcn_readfirstlane(oa[0] ^ ob[0]) == 0x12345u) chain(sl, oa, ob, rv);
 #else
-    chain(sl, oa, ob);
+    chain(sl, oa, ob, rv);
 #endif
     if (kLag && ordered && half) publish_applied(n);
   };
@@ -2368,9 +2437,11 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     task(n, s0, s1);
     if (n + kBsWaves >= ntask) break;
     n += kBsWaves;
+    next_row();
     task(n, s1, s0);
     if (n + kBsWaves >= ntask) break;
     n += kBsWaves;
+    next_row();
   }
   if (ordered && half == 0) publish_stored(n);  // the wave's last task
   stamp();
