@@ -42,6 +42,46 @@ def test_header_symbols_exported():
     assert N.source_id() == __graft_entry__.source_id()
 
 
+def test_every_included_source_is_hashed():
+    """fks_source_id() hashes the Makefile's SRCS: every csrc/*.hip and *.cpp and every file
+    they #include (transitively) from csrc/ or include/ must be on that list, or a header
+    added later would go unhashed and a stale prebuilt libfks.so pass for this tree's; and
+    __graft_entry__.SRCS, which recomputes the id, must be the same list in the same order."""
+    import glob
+
+    import __graft_entry__
+    pkg = os.path.join(ROOT, "fate-llm_amd")
+    csrc = os.path.join(pkg, "csrc")
+    with open(os.path.join(pkg, "Makefile")) as f:
+        mk = f.read().replace("\\\n", " ")
+    var = dict(re.findall(r"^(\w+)\s*:=\s*(.*)$", mk, re.M))
+    line = var["SRCS"]
+    while "$(" in line:
+        line = re.sub(r"\$\((\w+)\)", lambda m: var[m.group(1)], line)
+    srcs = line.split()
+    assert len(srcs) == len(set(srcs)), "a file is listed twice"
+    listed = {os.path.normpath(os.path.join(pkg, s)) for s in srcs}
+    todo = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.cpp")))
+    assert todo, "no sources found"
+    seen = set()
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path in seen:
+            continue
+        seen.add(path)
+        with open(path) as f:
+            incs = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+        for inc in incs:
+            for d in (os.path.dirname(path), csrc, os.path.join(ROOT, "include")):
+                cand = os.path.join(d, inc)
+                if os.path.isfile(cand):
+                    todo.append(cand)
+                    break
+    unhashed = sorted(os.path.relpath(p, pkg) for p in seen - listed)
+    assert not unhashed, f"built into libfks.so but not in the Makefile's SRCS: {unhashed}"
+    assert tuple(srcs) == tuple(__graft_entry__.SRCS)
+
+
 def test_fks_tensor_layout_matches_header():
     N, _ = _lib()
     assert ctypes.sizeof(N.FksTensor) == 32
