@@ -1597,6 +1597,88 @@ int fks_delta_apply(const fks_tensor* t, int32_t nt, const float* delta, const d
   });
 }
 
+// ---- seed-basis projection (torch_rocm stream) ----
+// bytes of block partials a launch over `items` work items writes (fks_project.hip)
+static size_t project_ws_bytes(int64_t items) {
+  return std::max<size_t>(sizeof(double) * (size_t)kPhxSeeds * (size_t)project_grid(items), 256);
+}
+
+// the calls take the torch_rocm stream only: every error is raised from the arguments alone
+static void project_check_stream(const fks_tensor* t, int nt) {
+  if (nt == 0 || rocm_stream(t, nt)) return;
+  throw Error(-FKS_ENOTSUP, std::string("fks_project: the torch_cpu stream (the CPU generator's MT19937 stream") +
+                                (libm_flavour(t, nt) ? ", FKS_LIBM flavour" : "") +
+                                ") is not supported; projection is built for FKS_STREAM_ROCM (torch_rocm) only");
+}
+
+int fks_project_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    project_check_stream(t, nt);
+    // a shard walks at most the whole list's items; the passes of kPhxSeeds seeds follow
+    // each other on the stream and share the partials
+    PhxPlan geo;
+    phx_geometry(t, nt, nullptr, &geo, 0);
+    *bytes = project_ws_bytes(geo.items);
+  });
+}
+
+int fks_project(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
+                int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    if (nshards < 1 || shard < 0 || shard >= nshards) throw Error(-FKS_EINVAL, "bad shard");
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (k > 0 && (!vec || ((uintptr_t)vec % 8) != 0)) throw Error(-FKS_EINVAL, "null or misaligned vector");
+    if (k > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned projection output");
+    project_check_stream(t, nt);
+    if (k == 0) return;
+    // the geometry on the host first (as fks_shard_census): the workspace is checked before
+    // anything is allocated or launched
+    const uint64_t base = (uint64_t)(uintptr_t)vec;
+    int64_t lo = 0, hi = 0;
+    if (nt > 0) {
+      PhxPlan geo;
+      phx_geometry(t, nt, nullptr, &geo, base);
+      if (geo.nt > 0 && geo.items > 0) {
+        lo = phx_boundary(&geo, shard, nshards);
+        hi = phx_boundary(&geo, shard + 1, nshards);
+      }
+    }
+    if (lo >= hi) {  // nothing in this shard: every projection is +0
+      const hipError_t e = hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)k, (hipStream_t)stream);
+      if (e != hipSuccess) throw Error(-FKS_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+      return;
+    }
+    const size_t need = project_ws_bytes(hi - lo);
+    if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < need)
+      throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(need) + " bytes, got " +
+                                   std::to_string(ws_bytes));
+    std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+    const PhxPlan* P = get_phx_plan(t, nt, nullptr, base);  // the table fks_delta_accumulate uses for this base
+    ProjectArgs a{};
+    a.t = static_cast<const PhxTensor*>(P->dev);
+    a.nt = P->nt;
+    a.partial = static_cast<double*>(workspace);
+    a.item_lo = lo;
+    a.item_hi = hi;
+    const int grid = project_grid(hi - lo);
+    for (int s0 = 0; s0 < k; s0 += kPhxSeeds) {
+      const int nb = std::min(kPhxSeeds, k - s0);
+      for (int j = 0; j < nb; j++) a.seeds[j] = seeds[s0 + j];
+      a.nseeds = nb;
+      int rc = timed(0, stream, [&] { return launch_project(a, stream); });
+      if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_kernel launch: ") +
+                                                       (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
+      rc = launch_project_reduce(a.partial, grid, nb, dev_out + s0, stream);
+      if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_reduce_kernel launch: ") +
+                                                       (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
+    }
+  });
+}
+
 }  // extern "C"
 
 namespace fks {

@@ -302,6 +302,23 @@ struct DigestArgs {
 };
 int launch_digest(const DigestArgs& a, void* stream);
 
+// ---- seed-basis projection on the torch_rocm stream (fks_project.hip) ----
+// One pass of at most kPhxSeeds seeds over the items [item_lo, item_hi) of a kModeDelta
+// table (the entries point into the f32 vector): block b leaves its per-seed f64 sums in
+// partial[b][kPhxSeeds]; launch_project_reduce adds them in block order into out[0, nseeds).
+struct ProjectArgs {
+  uint64_t seeds[kPhxSeeds];
+  const PhxTensor* t;   // sorted by item0
+  double* partial;      // [project_grid(item_hi - item_lo)][kPhxSeeds]
+  int64_t item_lo;
+  int64_t item_hi;
+  int32_t nt;
+  int32_t nseeds;
+};
+int project_grid(int64_t items);  // workgroups of a launch over `items` work items on the current device
+int launch_project(const ProjectArgs& a, void* stream);
+int launch_project_reduce(const double* partial, int nblocks, int nseeds, double* out, void* stream);
+
 // launchers (fks_device.hip); return hipError_t as int
 int launch_jump(const JumpArgs& a, int nseeds, void* stream);
 int launch_apply(int dtype, const ApplyArgs& a, void* stream);

@@ -1,0 +1,252 @@
+// fks_project.hip -- seed-basis projection on the torch_rocm stream (include/fks.h
+// fks_project): out[s] = <vec, z_s> over the elements one element shard owns, the adjoint of
+// fks_delta_accumulate (delta = Z c; this is Z^T v).
+//
+// fks_project_kernel walks the work items of the call's PhxTensor table (fks_internal.h; the
+// table of a kModeDelta call, whose entries point into the f32 vector) as
+// fks_philox_vec_kernel does: a thread takes a GROUP of kProjVec consecutive items (idx0 ..
+// idx0 + 7 of one row j), 32 elements that lie in four 8-element runs of the vector; a
+// wave's 64 groups are consecutive and their tensor is looked up with wave-uniform indices
+// from the LDS copy of the table.  Per group the seeds of the pass run in order: eight
+// Philox4x32-10 calls (round 1, which multiplies the counter only, computed once per item
+// for all the seeds), the four z of each in the tensor's dtype -- the values fks_normal
+// writes --, and 32 products (double)v * (double)z, each EXACT (24 + 24 significand bits),
+// summed into one f64 partial by fma (one rounding per addition).
+//
+// The reduction uses no floating-point atomic and has one fixed order: the group partial of
+// seed k is summed over the wave by an xor butterfly (every lane ends with the same bits;
+// lanes without a group, or whose group belongs to another dtype's pass, enter +0), lane k
+// adds the wave's total to its running sum, so a wave carries one f64 per seed instead of
+// 32 per lane; at the end the block's waves are added in wave order through LDS into
+// partial[block][k], and fks_project_reduce_kernel adds the blocks' partials in block order.
+// The grid is a function of the device and the item range only, so a call's result depends
+// on the device, the tensor list, the shard and the seeds, and on nothing else.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "fks_internal.h"
+#include "fks_dev_zgen.h"
+
+namespace fks {
+namespace {
+
+constexpr int kProjVec = 8;           // work items per thread (fks_kern_philox.h kPhxVec)
+constexpr int kProjThreads = 256;
+constexpr int kProjWaves = kProjThreads / 64;
+// A/B switches (make variant_project NAME=x DEFS="-D..."; profiles/r08_project_ab.log has the runs):
+#ifndef FKS_PROJ_WG_PER_CU   // grid cap: workgroups per CU, as fks_philox_vec_kernel's.  7B bf16 layout, one
+#define FKS_PROJ_WG_PER_CU 16  // 32-seed launch: 3 (the residency at 156 VGPRs) 135.0 ms, 8 125.8-126.3, 16 123.1
+#endif
+#ifndef FKS_PROJ_LEAN        // 1: the vector stays f32 (converted inside the seed loop) and round 1 is redone per
+#define FKS_PROJ_LEAN 0      // seed: 126 VGPRs and four waves per SIMD instead of 156 and three, but 140.0 ms
+#endif
+#ifndef FKS_PROJ_MIN_WAVES   // launch-bounds waves per SIMD (0: none).  4 with FKS_PROJ_LEAN: 147.2 ms; 4 or 5
+#define FKS_PROJ_MIN_WAVES 0 // on the kept form spill to scratch
+#endif
+constexpr int kProjWgPerCu = FKS_PROJ_WG_PER_CU;
+constexpr int kProjLdsTensors = 512;  // tables of at most this many entries are copied to LDS
+constexpr int kProjAccBytes = kProjWaves * kPhxSeeds * 8;  // the waves' sums, in front of the table
+static_assert(kPhxSeeds <= 64, "lane k of a wave keeps seed k's sum");
+static_assert(kProjAccBytes % 16 == 0, "the LDS table starts 16-byte aligned");
+
+typedef __attribute__((address_space(1))) const u32x4_t proj_gu128;
+typedef __attribute__((address_space(1))) const float proj_gf32;
+
+// the last table entry whose first item is <= it, at or after lo (items only grow; a wave's
+// next groups lie mostly in the same or the next tensor: a few probes, then bisection)
+template <class Tab>
+__device__ __forceinline__ int proj_find_t(Tab tab, int nt, int64_t it, int lo, int probes) {
+  for (int p = 0; p < probes; p++) {
+    if (lo + 1 >= nt || tab[lo + 1].item0 > it) return lo;
+    ++lo;
+  }
+  int hi = nt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].item0 <= it) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the 32 vector elements of the group at items r0 .. r0 + 7 of T: v[i][q] = element
+// idx0 + q + S (4 j + i), +0 for an element past the tensor's end.  Whole 16-byte runs where
+// the data is 16-byte aligned (idx0 and S are multiples of 8) and the four runs lie inside
+// the tensor; per element otherwise (a tensor's last row, an unaligned vector).
+__device__ __forceinline__ void proj_load(const PhxTensor& T, uint32_t idx0, uint64_t j, float v[4][kProjVec]) {
+  const int64_t S = (int64_t)T.stride;
+  const int64_t e0 = (int64_t)idx0 + S * (int64_t)(4 * j);
+  if ((T.flags & kPhxP16) && e0 + 3 * S + kProjVec <= T.numel) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      proj_gu128* q = reinterpret_cast<proj_gu128*>(T.ptr + (uint64_t)(e0 + S * i) * 4u);
+      const u32x4_t x = q[0], y = q[1];
+      const uint32_t w[kProjVec] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+#pragma unroll
+      for (int k = 0; k < kProjVec; k++) v[i][k] = __uint_as_float(w[k]);
+    }
+    return;
+  }
+  proj_gf32* p = reinterpret_cast<proj_gf32*>(T.ptr);
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int k = 0; k < kProjVec; k++) {
+      const int64_t e = e0 + S * i + k;
+      v[i][k] = e < T.numel ? p[e] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ double proj_wave_sum(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+
+// Every seed of the pass over the wave's groups whose tensors draw dtype DT (`mine`: this
+// lane has such a group): the whole wave runs this, lanes that are not `mine` enter +0.
+template <int DT>
+__device__ __forceinline__ void proj_seeds(const ProjectArgs& a, uint64_t ctr, uint32_t idx0,
+                                           const float v[4][kProjVec], bool mine, int lane, double& acc) {
+  PhxRound1 r1[kProjVec];
+#pragma unroll
+  for (int q = 0; q < kProjVec; q++) r1[q] = philox_round1(ctr, idx0 + (uint32_t)q);
+  for (int k = 0; k < a.nseeds; k++) {
+    const uint64_t seed = a.seeds[k];  // wave-uniform: scalar loads
+    double part = 0.0;
+#pragma unroll
+    for (int q = 0; q < kProjVec; q++) {
+#if FKS_PROJ_LEAN
+      uint32_t iq = idx0 + (uint32_t)q;
+      asm volatile("" : "+v"(iq));  // opaque: keeps round 1 inside the loop
+      const uint4 w = philox4x32_10(philox_round1(ctr, iq), seed);
+#else
+      const uint4 w = philox4x32_10(r1[q], seed);
+#endif
+      f32x2_t zA, zB;
+      if constexpr (DT == FKS_BF16) {
+        phx_z_bf16(w, zA, zB);
+      } else {
+        phx_box_muller2(w, zA, zB);
+        zA = (f32x2_t){phx_cast<DT>(zA.x), phx_cast<DT>(zA.y)};
+        zB = (f32x2_t){phx_cast<DT>(zB.x), phx_cast<DT>(zB.y)};
+      }
+      // exact products, one rounding per addition
+      float x0 = v[0][q], x1 = v[1][q], x2 = v[2][q], x3 = v[3][q];
+#if FKS_PROJ_LEAN
+      asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));  // opaque: the f64 conversions stay in the loop
+#endif
+      part = __fma_rn((double)x0, (double)zA.x, part);
+      part = __fma_rn((double)x1, (double)zA.y, part);
+      part = __fma_rn((double)x2, (double)zB.x, part);
+      part = __fma_rn((double)x3, (double)zB.y, part);
+    }
+    const double total = proj_wave_sum(mine ? part : 0.0);
+    acc += lane == k ? total : 0.0;
+  }
+}
+
+template <class Tab>
+__device__ __forceinline__ void proj_walk(const ProjectArgs& a, Tab tab, int lane, double& acc) {
+  const int64_t step = (int64_t)gridDim.x * kProjThreads * kProjVec;
+  int64_t wb = rfl64(a.item_lo + ((int64_t)blockIdx.x * kProjThreads + (int64_t)(threadIdx.x & ~63u)) * kProjVec);
+  int ts = 0;
+  // wb and the loop are wave-uniform: every lane of the wave reaches the butterflies
+  for (; wb < a.item_hi; wb += step) {
+    ts = __builtin_amdgcn_readfirstlane(proj_find_t(tab, a.nt, wb, ts, 2));
+    const int64_t wend = wb + 64 * kProjVec < a.item_hi ? wb + 64 * kProjVec : a.item_hi;
+    const bool one = ts + 1 >= a.nt || tab[ts + 1].item0 >= wend;  // the whole wave in tensor ts
+    const int64_t it = wb + (int64_t)lane * kProjVec;
+    const bool active = it < a.item_hi;
+    const int ti = one ? ts : proj_find_t(tab, a.nt, active ? it : a.item_hi - 1, ts, 0);
+    const PhxTensor T = tab[ti];
+    // (a lane without a group keeps a valid entry; its idx0 and j only feed a discarded z)
+    const int64_t r0 = active ? it - T.item0 : 0;
+    const uint32_t idx0 = (uint32_t)(r0 % (int64_t)T.stride);
+    const uint64_t j = (uint64_t)(r0 / (int64_t)T.stride);
+    float v[4][kProjVec];
+    if (active) {
+      proj_load(T, idx0, j, v);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int k = 0; k < kProjVec; k++) v[i][k] = 0.0f;
+    }
+    // one pass per dtype present in the wave (wave-uniform branches: a wave lies in one
+    // tensor, or in neighbours of one dtype, nearly always)
+    const bool m32 = active && T.dtype == FKS_F32, mbf = active && T.dtype == FKS_BF16,
+               m16 = active && T.dtype != FKS_F32 && T.dtype != FKS_BF16;
+    if (__any(m32)) proj_seeds<FKS_F32>(a, T.off4 + j, idx0, v, m32, lane, acc);
+    if (__any(mbf)) proj_seeds<FKS_BF16>(a, T.off4 + j, idx0, v, mbf, lane, acc);
+    if (__any(m16)) proj_seeds<FKS_F16>(a, T.off4 + j, idx0, v, m16, lane, acc);
+  }
+}
+
+#if FKS_PROJ_MIN_WAVES
+__global__ __launch_bounds__(kProjThreads, FKS_PROJ_MIN_WAVES) void fks_project_kernel(ProjectArgs a) {
+#else
+__global__ __launch_bounds__(kProjThreads) void fks_project_kernel(ProjectArgs a) {
+#endif
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_proj[];
+  double* s_acc = reinterpret_cast<double*>(s_proj);                              // [kProjWaves][kPhxSeeds]
+  PhxTensor* s_tab = reinterpret_cast<PhxTensor*>(s_proj + kProjAccBytes);
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = (int)(threadIdx.x >> 6);
+  double acc = 0.0;  // lane k < kPhxSeeds: the wave's sum for seed k
+  if (a.nt <= kProjLdsTensors) {
+    constexpr int W = (int)(sizeof(PhxTensor) / 4);
+    for (int i = (int)threadIdx.x; i < a.nt * W; i += kProjThreads)
+      reinterpret_cast<uint32_t*>(s_tab)[i] = reinterpret_cast<const uint32_t*>(a.t)[i];
+    __syncthreads();
+    proj_walk(a, (const PhxTensor*)s_tab, lane, acc);
+  } else {
+    proj_walk(a, a.t, lane, acc);
+  }
+  if (lane < kPhxSeeds) s_acc[wave * kPhxSeeds + lane] = acc;
+  __syncthreads();
+  if (threadIdx.x < (unsigned)kPhxSeeds) {
+    double s = s_acc[threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kProjWaves; w++) s += s_acc[w * kPhxSeeds + (int)threadIdx.x];
+    a.partial[(size_t)blockIdx.x * kPhxSeeds + threadIdx.x] = s;
+  }
+}
+
+// one wave per seed: lane l adds the partials of blocks l, l + 64, ... in order, then the
+// lanes' sums meet in the butterfly
+__global__ __launch_bounds__(64) void fks_project_reduce_kernel(const double* partial, int nblocks, double* out) {
+  const int k = (int)blockIdx.x;
+  double s = 0.0;
+  for (int b = (int)threadIdx.x; b < nblocks; b += 64) s += partial[(size_t)b * kPhxSeeds + k];
+  s = proj_wave_sum(s);
+  if (threadIdx.x == 0) out[k] = s;
+}
+
+}  // namespace
+
+int project_grid(int64_t items) {
+  const int64_t groups = (items + kProjVec - 1) / kProjVec;
+  const int64_t want = (groups + kProjThreads - 1) / kProjThreads;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)kProjWgPerCu * device_cu_count()));
+}
+
+int launch_project(const ProjectArgs& a, void* stream) {
+  const int64_t items = a.item_hi - a.item_lo;
+  if (a.nseeds < 1 || a.nseeds > kPhxSeeds || a.nt < 1 || items <= 0 || !a.partial) return -FKS_EINVAL;
+  // groups never straddle a tensor or the shard: every boundary is a multiple of 256 items
+  if (a.item_lo % kProjVec != 0 || items % kProjVec != 0) return -FKS_EINVAL;
+  const size_t lds = (size_t)kProjAccBytes + (a.nt <= kProjLdsTensors ? sizeof(PhxTensor) * (size_t)a.nt : 0);
+  hipLaunchKernelGGL(fks_project_kernel, dim3((unsigned)project_grid(items)), dim3(kProjThreads), lds,
+                     (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int launch_project_reduce(const double* partial, int nblocks, int nseeds, double* out, void* stream) {
+  if (nseeds < 1 || nseeds > kPhxSeeds || nblocks < 1) return -FKS_EINVAL;
+  hipLaunchKernelGGL(fks_project_reduce_kernel, dim3((unsigned)nseeds), dim3(64), 0, (hipStream_t)stream, partial,
+                     nblocks, out);
+  return (int)hipGetLastError();
+}
+
+}  // namespace fks

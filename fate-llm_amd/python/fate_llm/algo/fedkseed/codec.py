@@ -147,7 +147,10 @@ def _f32(x: float) -> float:
 class _Batch:
     """fks_tensor array for a list of specs (keeps contiguous staging copies alive)."""
 
-    def __init__(self, specs: Sequence[ParamSpec], stream_mode=None):
+    def __init__(self, specs: Sequence[ParamSpec], stream_mode=None, stage: bool = True):
+        # stage=False: the call never touches the tensors' data (it reads their sizes, dtypes
+        # and flags; the addresses only key the plan cache), so a non-contiguous tensor gets
+        # no staging copy -- its own, stable address is passed
         self.specs = list(specs)
         self.copies = []  # (original, contiguous staging) pairs to write back
         self.device = None
@@ -169,7 +172,7 @@ class _Batch:
         arr = (N.FksTensor * max(1, len(self.specs)))()
         for i, sp in enumerate(self.specs):
             t = sp.tensor
-            if not t.is_contiguous():
+            if stage and not t.is_contiguous():
                 c = t.contiguous()
                 self.copies.append((t, c))
                 t = c
@@ -622,6 +625,50 @@ def delta_apply(specs: Sequence[ParamSpec], delta: torch.Tensor, decays: Sequenc
         N.check(L.fks_delta_apply(ctypes.addressof(b.arr), b.n, delta.data_ptr(), d.ctypes.data, ws.data_ptr(),
                                   nbytes, _stream_handle(b.device)))
         b.finish()
+
+
+def project(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor, stream_mode=None,
+            shard: int = 0, nshards: int = 1) -> torch.Tensor:
+    """Seed-basis projection (include/fks.h fks_project), the adjoint of ``delta_accumulate``:
+    out[s] = <vec, z_s> over the non-frozen specs' elements that element shard ``shard`` of
+    ``nshards`` owns (``shard_range``; the shards' results add up to the whole call's), z_s
+    the torch_rocm stream's draw for seeds[s] in each spec's dtype; ``vec`` is the f32
+    concatenation of the specs' elements (frozen specs keep their range, draw and contribute
+    nothing).  Exact products, f64 sums in one fixed order: the same call gives the same
+    bits.  Returns a float64[K] tensor on the specs' device, queued on the current stream --
+    no synchronisation once the (spec list, vec address) pair has a cached plan: the first
+    call with a vec at a new address builds and uploads the tensor table (a device allocation
+    and a synchronous copy, as delta_accumulate's first call with a new delta buffer), so a
+    caller that projects repeatedly should reuse its vec buffer.  An empty tensor for no
+    seeds.  Draws nothing from torch's generators
+    and leaves them alone.  torch_rocm stream only: a call that resolves to torch_cpu raises
+    NotImplementedError."""
+    specs = list(specs)
+    device = specs[0].tensor.device if specs else vec.device
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: project() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws)")
+    b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    if b.device is None:
+        b.device = vec.device
+    _check_delta(b, vec)
+    s = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    out = torch.empty(len(s), dtype=torch.float64, device=b.device)
+    if not len(s):
+        return out
+    if not vec.numel():  # no element anywhere: every projection is +0
+        return out.zero_()
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_project_workspace_size(ctypes.addressof(b.arr), b.n, len(s), ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_project(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), vec.data_ptr(), int(shard),
+                              int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    return out  # ws goes back to torch's allocator in stream order
 
 
 # ---------------------------------------------------------------- model fingerprint (FKSD-1)

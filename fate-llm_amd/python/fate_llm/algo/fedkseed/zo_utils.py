@@ -173,6 +173,84 @@ def reconstruct_seed_sharded_(param_groups: List[dict], seeds: Sequence[int], va
     return len(keep)
 
 
+def _projection_inputs(param_groups: List[dict], vectors):
+    """(specs, vec, N): the parameters of every group in the codec's order -- one that does
+    not require grad is frozen: it draws its z and contributes nothing --, the vectors
+    flattened into the f32 concatenation codec.project reads (a frozen parameter's range is
+    zero), and the number of non-frozen elements."""
+    params = [p for g in param_groups for p in g["params"]]
+    if vectors is None:
+        vectors = [p.grad if p.requires_grad else None for p in params]
+    vectors = list(vectors)
+    if len(vectors) != len(params):
+        raise ValueError(f"one vector per parameter: {len(params)} parameters, {len(vectors)} vectors")
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    if not params:
+        return specs, None, 0
+    total = sum(p.numel() for p in params)
+    vec = torch.empty(total, dtype=torch.float32, device=params[0].device)
+    at = n_live = 0
+    for i, (p, v) in enumerate(zip(params, vectors)):
+        dst = vec[at:at + p.numel()]
+        at += p.numel()
+        if not p.requires_grad:
+            dst.zero_()
+            continue
+        if v is None:
+            raise ValueError(f"parameter {i} requires grad and has no vector (its .grad is None)")
+        if not v.is_floating_point() or v.numel() != p.numel():
+            raise ValueError(f"vector {i}: a floating-point tensor of {p.numel()} elements is needed, "
+                             f"got {v.dtype} {tuple(v.shape)}")
+        dst.copy_(v.detach().reshape(-1))
+        n_live += p.numel()
+    return specs, vec, n_live
+
+
+def seed_projections(param_groups: List[dict], seeds: Sequence[int], vectors=None, stream_mode=None) -> torch.Tensor:
+    """g_k = <v, z_k> for every seed: the exact directional derivatives of the K seed
+    candidates along a dense vector -- with v the gradient, one backward pass instead of two
+    forward passes per seed, and no finite-difference noise; the K scalars the wire carries.
+
+    ``vectors``: one tensor per parameter of the groups, in order, of any float dtype (the
+    entry of a parameter that does not require grad is ignored and may be None); default:
+    every parameter's ``.grad`` (a missing grad on a parameter that requires grad is an
+    error).  z_k is the stream ``directional_derivative_step`` draws for seed k: every
+    parameter draws, in each one's own dtype; those that do not require grad contribute
+    nothing.  Mind the consequence: ``directional_derivative_step`` itself freezes nothing
+    -- like the reference's, it updates every parameter of the groups, whatever its
+    ``requires_grad`` -- so the K values are the exact derivatives of the step it applies
+    only when every parameter of the groups requires grad (the groups
+    ``pytorch_utils.get_optimizer_parameters_grouped_with_decay`` builds hold only such
+    parameters); with a parameter that does not, the step moves it along z as well and its
+    term is missing here.
+    The vectors are read as f32, and each call lays them out in a new f32 buffer of the
+    model's size, so its first launch also builds the buffer's tensor table (an allocation and
+    a synchronous upload; codec.project).  Returns float64[K] on the parameters' device,
+    queued on the current stream (codec.project: exact products, f64 sums, bit-reproducible;
+    torch_rocm stream only).  torch's generators are left alone."""
+    specs, vec, _ = _projection_inputs(param_groups, vectors)
+    if vec is None:
+        return torch.zeros(len(seeds), dtype=torch.float64)
+    return codec.project(specs, seeds, vec, stream_mode=stream_mode)
+
+
+def fit_seed_scalars(param_groups: List[dict], seeds: Sequence[int], delta_vectors, stream_mode=None) -> torch.Tensor:
+    """The (seed, scalar) form of a dense update: ``seed_projections(delta) / N``, N the
+    number of elements of the parameters that require grad -- how a fine-tuned checkpoint's
+    or a FedAvg round's delta enters a running federation.
+
+    An approximation: the least-squares scalars in the candidates' span are
+    (Z^T Z)^-1 Z^T delta, and the Gram matrix Z^T Z equals N I only in expectation -- its
+    diagonal deviates from N by O(sqrt(2 N)), its off-diagonal entries are O(sqrt(N)) --, so
+    these scalars differ from the least-squares ones by a relative error of order
+    sqrt(K / N): negligible for K << N.  What is fitted is the projection of delta on the
+    K-seed subspace, a share of about K / N of a generic delta's energy."""
+    specs, vec, n_live = _projection_inputs(param_groups, delta_vectors)
+    if vec is None or n_live == 0:
+        raise ValueError("fit_seed_scalars: no parameter requires grad")
+    return codec.project(specs, seeds, vec, stream_mode=stream_mode) / float(n_live)
+
+
 def build_seed_candidates(k, low=0, high=2**32):
     """K seed candidates drawn from the global torch generator."""
     return torch.randint(low, high, size=(k,), dtype=torch.long)

@@ -272,6 +272,37 @@ int fks_delta_accumulate(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
 int fks_delta_apply(const fks_tensor* t, int32_t nt, const float* delta, const double* decay, void* workspace,
                     size_t ws_bytes, void* stream);
 
+/* ---- seed-basis projection: g_s = <v, z_s> (FKS_STREAM_ROCM only) ----
+ * The adjoint of fks_delta_accumulate (delta = Z c): a dense f32 vector expressed in the K
+ * seeds, Z^T v.  With v = grad f these are the exact directional derivatives of all K
+ * candidates from one backward pass -- the wire's own K scalars (fedkseed.py:136-141 applies
+ * them) --; with v a dense delta, Z^T v / N are its least-squares scalars in the candidates'
+ * span for K << N (the Gram matrix Z^T Z is N I in expectation only); and
+ * |Z^T g|^2 / (N |g|^2) is the share of a gradient the K-seed subspace captures.
+ *
+ * fks_project: dev_out[s] = sum over the non-frozen tensors i and the elements e that element
+ * shard `shard` of `nshards` owns of (double)vec[cum_i + e] * (double)z_s(i, e), s < k.
+ * vec follows fks_delta_accumulate's buffer: f32, device memory, 8-byte aligned, the tensors'
+ * concatenation (cum_i = sum of numel over the tensors before i; frozen and empty tensors
+ * keep their range).  z_s is the FKS_STREAM_ROCM draw for seeds[s] in the tensor's dtype, the
+ * values fks_normal writes; frozen tensors advance the Philox offset and contribute nothing.
+ * The shards are fks_directional_step_shard's runs of whole Philox rows (fks_shard_census);
+ * the shards' results add up to the whole call's.  Every product is exact in f64 (24 + 24
+ * significand bits) and the additions are f64 in ONE fixed order, with no floating-point
+ * atomic: the result is bit-reproducible for the same device, tensor list, shard and seeds
+ * (the order is not the reference order of any torch reduction; the error of any f64 order
+ * is at most n 2^-52 sum |v z| over the n terms).  dev_out (k doubles, device memory, 8-byte
+ * aligned) is OVERWRITTEN in stream order, never accumulated into; seeds go in passes of 32.
+ * lr, wd and the other flags are ignored; the tensors' data pointers are not read.  Draws
+ * nothing from torch's generators.  k == 0, nt == 0 and all-empty lists succeed; k > 0 with no
+ * element in the shard zeroes dev_out.  Workspace: fks_project_workspace_size (8-byte aligned).
+ * Errors, raised before any device work: null or misaligned vec / dev_out with k > 0, a bad
+ * shard, too small a workspace: -FKS_EINVAL; tensors of the CPU generator's stream (no
+ * FKS_STREAM_ROCM, with or without FKS_LIBM): -FKS_ENOTSUP.                               */
+int fks_project_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, size_t* bytes);
+int fks_project(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
+                int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
