@@ -40,6 +40,7 @@ typedef __attribute__((address_space(1))) _Float16 gf16;
 typedef __attribute__((address_space(1))) uint32_t gu32;
 
 typedef __attribute__((address_space(1))) uint64_t gu64;
+typedef uint16_t u16x2_t __attribute__((ext_vector_type(2)));
 
 template <>
 struct Traits<FKS_F32> {
@@ -65,6 +66,13 @@ struct Traits<FKS_BF16> {
   __device__ static uint32_t lo(Pair v) { return v & 0xffffu; }
   __device__ static uint32_t hi(Pair v) { return v >> 16; }
   __device__ static Pair pack(uint32_t l, uint32_t h) { return (l & 0xffffu) | (h << 16); }
+  // one element as the bits of its f32 value: a 16-bit load into the high half of a zeroed
+  // register (global_load_short_d16_hi), a 16-bit store of the high half (v is bf16-exact)
+  __device__ static uint32_t load_hi(uint64_t a) {
+    const u16x2_t v = {(uint16_t)0, *reinterpret_cast<const gu16*>(a)};
+    return __builtin_bit_cast(uint32_t, v);
+  }
+  __device__ static void store_hi(uint64_t a, uint32_t v) { *reinterpret_cast<gu16*>(a) = (uint16_t)(v >> 16); }
   __device__ static uint32_t bits(float v) { return __float_as_uint(v) >> 16; }  // v is bf16-exact
   __device__ static uint32_t load_raw(uint64_t p, int64_t i) { return reinterpret_cast<const gu16*>(p)[i]; }
   __device__ static float cvt(uint32_t r) { return __uint_as_float(r << 16); }
@@ -140,6 +148,19 @@ __device__ __forceinline__ f32x2_t rnd2(f32x2_t x) {
   f32x2_t r;
   r.x = Traits<DT>::rnd(x.x);
   r.y = Traits<DT>::rnd(x.y);
+  return r;
+}
+
+// g z with g one half of the SGPR pair gg = {g of the even seed, g of the odd seed}: op_sel
+// picks half H for both result lanes, so two seeds' scalars share one SGPR pair (a pure
+// VALU instruction: no counter, nothing the compiler has to wait for)
+template <int H>
+__device__ __forceinline__ f32x2_t pk_mul_half(uint64_t gg, f32x2_t z) {
+  f32x2_t r;
+  if (H == 0)
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "s"(gg), "v"(z));
+  else
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "s"(gg), "v"(z));
   return r;
 }
 

@@ -41,6 +41,21 @@ constexpr int kBsFence = 8;      // slice kernel: compiler fence after every 8 s
 #ifndef FKS_BS_R_VMEM            // slice kernel, wd 0 chain: of every byte column's 8 seeds, this many take R
 #define FKS_BS_R_VMEM 3          // from the device-global table through the vector-memory path, loaded ahead
 #endif                           // (0..8).  3: 2.3 % faster; 0, 1, 2, 4: no gain (profiles/r07_bs_colimit_ab.log)
+// slice kernel, wd 0 chain: the task path without lane-mask selects, neighbour exchanges and SGPR spills
+// (fks_kern_slice.h).  Kept as a set: 1.8 % faster than the parent together, while alone or in smaller sets
+// each of them is within +-1.7 % either way (profiles/r09_bs_taskpath_ab.log)
+#ifndef FKS_BS_D16               // 1: a lane loads and stores its two bf16 parameters as 16-bit halves,
+#define FKS_BS_D16 1             // no pair exchange with the neighbour lane
+#endif
+#ifndef FKS_BS_G32               // 1: two seeds' g per SGPR pair, the half chosen by op_sel on the packed
+#define FKS_BS_G32 1             // multiply (32 SGPRs instead of 64: no SGPR spills)
+#endif
+#ifndef FKS_BS_ROWMIN            // 1: the twist's row indices wrapped by unsigned min, the flip folded into
+#define FKS_BS_ROWMIN 1          // per-lane constants, no compare-and-select
+#endif
+#ifndef FKS_BS_FLIPMUX           // 1: the flip of the tempered planes as v_bitop3_b32 on a per-lane mask
+#define FKS_BS_FLIPMUX 1
+#endif
 #ifndef FKS_PHX_VEC_ITEMS        // torch_rocm few-seed kernel: work items per thread (8; A/B: 4), see
 #define FKS_PHX_VEC_ITEMS 8      // kPhxVec in fks_kern_philox.h
 #endif

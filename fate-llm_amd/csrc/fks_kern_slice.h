@@ -154,9 +154,25 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   const bool flip = ((lane >> 3) & 1) != 0;
   const bool odd = (lane & 1) != 0;
 
+  // The wd 0 chain's task path without lane-mask selects and neighbour exchanges, each lever
+  // with its switch (fks_device.hip; measured in profiles/r09_bs_taskpath_ab.log)
+  constexpr bool kWd0 = MODE == kModeUpdateWd0;
+  constexpr bool kD16 = kWd0 && FKS_BS_D16 != 0;          // parameters as 16-bit halves, no pair exchange
+  constexpr bool kG32 = kWd0 && FKS_BS_G32 != 0;          // two seeds' g per SGPR pair
+  constexpr bool kRowMin = kWd0 && FKS_BS_ROWMIN != 0;    // row indices wrapped by unsigned min
+  constexpr bool kFlipMux = kWd0 && FKS_BS_FLIPMUX != 0;  // the planes' flip as a bitwise mux
+  // all ones in the lanes whose first row is toff + 8 (pinned in a VGPR: a value the compiler
+  // sees through becomes the compare-and-select again)
+  uint32_t flipm = flip ? ~0u : 0u;
+  if (kFlipMux) asm volatile("" : "+v"(flipm));
+
   float gk[kBsSeeds];
 #pragma unroll
   for (int k = 0; k < kBsSeeds; k++) gk[k] = a.g[half ? k + sfirst : k];
+  uint64_t gg[kBsSeeds / 2];  // kG32: {g of seed 2k, g of seed 2k+1}
+#pragma unroll
+  for (int k = 0; k < kBsSeeds / 2; k++)
+    gg[k] = (uint64_t)rfl(__float_as_uint(gk[2 * k])) | ((uint64_t)rfl(__float_as_uint(gk[2 * k + 1])) << 32);
 
   // the lane's current segment (positions only grow)
   const int64_t wbase = (int64_t)kMtN * b0;  // stream position of the chunk's first word
@@ -213,7 +229,16 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // read and write the sink.
   using ST = Traits<MODE == kModeDelta ? FKS_F32 : FKS_BF16>;
   typedef typename ST::Pair Pair;
-  struct Slot { uint64_t addr; float lr, wd; uint32_t wdf; Pair raw; };
+  // kD16: every lane loads its own two elements instead, each as a 16-bit load whose value
+  // becomes the high half of a register -- the bits of the f32 value -- from one address
+  // (element toff; element toff + 8 lies 16 bytes on, the sink included: 4 KB), and stores the
+  // high halves back (global_store_short_d16_hi).  No exchange, no halves to pick or pack, no
+  // divergent pack; plain loads and stores, so the compiler counts vmcnt for them as for the
+  // pair (one more load per task behind the R loads' counted waits, one more store under
+  // publish_stored()'s vmcnt(0)).  The load is global_load_ushort and a shift, not
+  // global_load_short_d16_hi: with SRAM ECC a d16 load does not keep the register's other
+  // half, so the compiler does not select it.
+  struct Slot { uint64_t addr; float lr, wd; uint32_t wdf; Pair raw; uint32_t hi0, hi1; };
   auto fetch = [&](int n) -> Slot {
     Slot sl;
     const int u1 = kBsTaskWords * n + toff;
@@ -221,7 +246,12 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
       while (u1 >= seg_hi) { cur++; load_seg(); }
       const bool on = u1 < nwords && u1 >= seg_lo;
       sl.lr = seg_lr; sl.wd = seg_wd; sl.wdf = seg_wdf;
-      sl.addr = on ? seg_org + (uint64_t)(uint32_t)(u1 + (odd ? 7 : 0)) * kEs : (uint64_t)(uintptr_t)a.sink;
+      sl.addr = on ? seg_org + (uint64_t)(uint32_t)(u1 + (odd && !kD16 ? 7 : 0)) * kEs : (uint64_t)(uintptr_t)a.sink;
+      if (kD16) {
+        sl.hi0 = Traits<FKS_BF16>::load_hi(sl.addr);
+        sl.hi1 = Traits<FKS_BF16>::load_hi(sl.addr + 16);
+        return sl;
+      }
     } else {
       const int64_t s1 = wbase + u1;
       while (s1 >= seg_end) { cur++; load_seg(); }
@@ -244,19 +274,35 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // divided out once here and carried by next_row() from then on.
   constexpr int kRowStep = kBsWaves * kBsTaskWords % kMtN;
   int row = (kBsTaskWords * hw + toff) % kMtN;
+  // kRowMin: the wraps as unsigned min -- x in [0, 2 * 624): min(x, x - 624) is x below 624
+  // (x - 624 wraps to a huge value) and x - 624 from there on -- and the flip as the lane's
+  // two row offsets (8, 0) or (0, 8), so that no row index takes a compare and a select.
+  // The carried row is a valid row in every lane, also past the chunk's end: those lanes
+  // load rows nobody uses and only their stores are masked.
+  auto wrap = [](uint32_t x) -> uint32_t {
+    const uint32_t y = x - (uint32_t)kMtN;
+    return x < y ? x : y;
+  };
+  uint32_t rofa = flip ? 8u : 0u, rofb = flip ? 0u : 8u;
+  if (kRowMin) asm volatile("" : "+v"(rofa), "+v"(rofb));
   auto next_row = [&]() {
     if (!kInc) return;
+    if (kRowMin) {
+      row = (int)wrap((uint32_t)row + kRowStep);
+      return;
+    }
     row += kRowStep;
     if (row >= kMtN) row -= kMtN;
   };
   auto twist = [&](const int n, uint32_t (&oa)[8], uint32_t (&ob)[8]) {
     const int u1 = kBsTaskWords * n + toff;
     const bool valid = u1 < nwords;
-    const int i1 = valid ? (kInc ? row : u1 % kMtN) : 0;
-    const int ia = flip ? i1 + 8 : i1, ib = flip ? i1 : i1 + 8;  // first / second row
+    const int i1 = kRowMin ? row : valid ? (kInc ? row : u1 % kMtN) : 0;
+    // first / second row (i1 + 8 < 624: 624 is a multiple of 16 and i1 mod 16 < 8)
+    const int ia = kRowMin ? i1 + (int)rofa : flip ? i1 + 8 : i1, ib = kRowMin ? i1 + (int)rofb : flip ? i1 : i1 + 8;
     auto rows = [&](int i, uint32_t& av, uint32_t& am, uint32_t& au) {
-      const int iv = i + 1 < kMtN ? i + 1 : 0;
-      const int im = i < kMtN - kMtM ? i + kMtM : i - (kMtN - kMtM);
+      const int iv = kRowMin ? (int)wrap((uint32_t)i + 1u) : i + 1 < kMtN ? i + 1 : 0;
+      const int im = kRowMin ? (int)wrap((uint32_t)i + kMtM) : i < kMtN - kMtM ? i + kMtM : i - (kMtN - kMtM);
       av = sbase + 16u * (uint32_t)iv;
       am = sbase + 16u * (uint32_t)im;
       au = sbase + 7u * kBsChunkBytes + 16u * (uint32_t)i + 12u;
@@ -307,8 +353,10 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     bs::temper_low8(M2, o2);
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      oa[j] = flip ? o2[j] : o1[j];  // row toff: the radius uniforms
-      ob[j] = flip ? o1[j] : o2[j];  // row toff + 8: the angle uniforms
+      // row toff: the radius uniforms; row toff + 8: the angle uniforms (kFlipMux: the same
+      // choice as v_bitop3_b32 on the lane's mask)
+      oa[j] = kFlipMux ? bs::mux(flipm, o2[j], o1[j]) : flip ? o2[j] : o1[j];
+      ob[j] = kFlipMux ? bs::mux(flipm, o1[j], o2[j]) : flip ? o1[j] : o2[j];
     }
   };
 
@@ -348,7 +396,10 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
       bs::transpose8(ob);
     }
     f32x2_t p;
-    {
+    if (kD16) {
+      p.x = __uint_as_float(sl.hi0);
+      p.y = __uint_as_float(sl.hi1);
+    } else {
       const uint32_t keep = odd ? ST::hi(sl.raw) : ST::lo(sl.raw);
       const uint32_t got = swap_adjacent(odd ? ST::lo(sl.raw) : ST::hi(sl.raw));
       p.x = ST::cvt(odd ? got : keep);
@@ -373,11 +424,22 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     {
 #pragma unroll
       for (int k = 0; k < kBsSeeds; k++) {
-        if (FULL || k < nseeds) p = apply_pair<FKS_BF16, MODE>(p, z_of(k), gk[k], sl.lr, sl.wd, sl.wdf != 0, 0.0f);
+        if (FULL || k < nseeds) {
+          if (kG32)  // apply_pair's statements with g z from the shared SGPR pair
+            p = apply_tail<FKS_BF16, MODE>(p, rnd2<FKS_BF16>(k & 1 ? pk_mul_half<1>(gg[k >> 1], z_of(k)) : pk_mul_half<0>(gg[k >> 1], z_of(k))),
+                                           sl.lr, sl.wd, sl.wdf != 0);
+          else
+            p = apply_pair<FKS_BF16, MODE>(p, z_of(k), gk[k], sl.lr, sl.wd, sl.wdf != 0, 0.0f);
+        }
         // the lookups of one byte column (8 seeds) at a time: hoisting all 64 table reads
         // ahead of the chain would spill
         if ((k % kBsFence) == kBsFence - 1) asm volatile("" ::: "memory");
       }
+    }
+    if (kD16) {  // p is bf16-exact: the high halves are the elements
+      Traits<FKS_BF16>::store_hi(sl.addr, __float_as_uint(p.x));
+      Traits<FKS_BF16>::store_hi(sl.addr + 16, __float_as_uint(p.y));
+      return;
     }
     const uint32_t b1v = ST::bits(p.x), b2v = ST::bits(p.y);
     const uint32_t back = swap_adjacent(odd ? b1v : b2v);
