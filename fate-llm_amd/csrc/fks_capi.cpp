@@ -1672,9 +1672,119 @@ int fks_project(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t 
       int rc = timed(0, stream, [&] { return launch_project(a, stream); });
       if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_kernel launch: ") +
                                                        (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
-      rc = launch_project_reduce(a.partial, grid, nb, dev_out + s0, stream);
+      rc = launch_project_reduce(a.partial, grid, nb, 1, dev_out + s0, 0, stream);
       if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_reduce_kernel launch: ") +
                                                        (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
+    }
+  });
+}
+
+// fks_project_multi's workspace: the vector table of the whole call ([nvec][entries], uploaded
+// once per call) in front, then the block partials of one pass of at most kProjMaxVec vectors
+static size_t project_multi_table_bytes(int entries, int nvec) {
+  const size_t b = sizeof(ProjVecEntry) * (size_t)std::max(entries, 0) * (size_t)std::max(nvec, 0);
+  return (b + 255) / 256 * 256;
+}
+static size_t project_multi_ws_bytes(int64_t items, int entries, int nvec) {
+  return project_multi_table_bytes(entries, nvec) + (size_t)std::min(std::max(nvec, 1), kProjMaxVec) * project_ws_bytes(items);
+}
+
+int fks_project_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    project_check_stream(t, nt);
+    PhxPlan geo;
+    phx_geometry(t, nt, nullptr, &geo, 0);
+    *bytes = project_multi_ws_bytes(geo.items, geo.nt, nvec);
+  });
+}
+
+int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs, int32_t nvec,
+                      int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    if (nvec < 0) throw Error(-FKS_EINVAL, "negative vector count");
+    if (nshards < 1 || shard < 0 || shard >= nshards) throw Error(-FKS_EINVAL, "bad shard");
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (nvec > 0 && nt > 0 && !vecs) throw Error(-FKS_EINVAL, "null vector list");
+    for (int m = 0; m < nvec; m++)
+      for (int i = 0; i < nt; i++) {
+        if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
+        const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+        if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
+          throw Error(-FKS_EINVAL, "vector " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad vector dtype " +
+                                       std::to_string(v.dtype));
+        if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
+          throw Error(-FKS_EINVAL, "vector " + std::to_string(m) + ", tensor " + std::to_string(i) +
+                                       ": null or misaligned vector pointer");
+      }
+    if (k > 0 && nvec > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned projection output");
+    project_check_stream(t, nt);
+    if (k == 0 || nvec == 0) return;
+    // the geometry on the host first: the workspace is checked before anything is allocated
+    // or launched
+    PhxPlan geo;
+    int64_t lo = 0, hi = 0;
+    if (nt > 0) {
+      phx_geometry(t, nt, nullptr, &geo, 0);
+      if (geo.nt > 0 && geo.items > 0) {
+        lo = phx_boundary(&geo, shard, nshards);
+        hi = phx_boundary(&geo, shard + 1, nshards);
+      }
+    }
+    if (lo >= hi) {  // nothing in this shard: every projection is +0
+      const hipError_t e = hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)k * (size_t)nvec, (hipStream_t)stream);
+      if (e != hipSuccess) throw Error(-FKS_EHIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+      return;
+    }
+    const size_t tab_bytes = project_multi_table_bytes(geo.nt, nvec);
+    const size_t need = project_multi_ws_bytes(hi - lo, geo.nt, nvec);
+    if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < need)
+      throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(need) + " bytes, got " +
+                                   std::to_string(ws_bytes));
+    // every vector's piece per table entry (a tensor past 2^31 bytes has several entries)
+    std::vector<int64_t> start((size_t)nt, 0);  // the tensors' first elements in the concatenation
+    for (int i = 1; i < nt; i++) start[i] = start[i - 1] + t[i - 1].numel;
+    thread_local std::vector<ProjVecEntry> host;
+    host.assign((size_t)nvec * (size_t)geo.nt, ProjVecEntry{});
+    for (int m = 0; m < nvec; m++)
+      for (int e = 0; e < geo.nt; e++) {
+        const int i = geo.tensor_of[e];
+        const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+        ProjVecEntry& x = host[(size_t)m * (size_t)geo.nt + (size_t)e];
+        x.ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)(geo.elem0[e] - start[i]) * elem_size(v.dtype);
+        x.dtype = v.dtype;
+        x.flags = (x.ptr % 16u) == 0 ? kPhxP16 : 0u;
+      }
+    std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+    const PhxPlan* P = get_phx_plan(t, nt, nullptr, 0);  // geometry only: the key does not hold the vectors
+    if (P->nt != geo.nt) throw Error(-FKS_EINVAL, "torch_rocm plan does not match the call's geometry");
+    hipError_t e = hipMemcpyAsync(workspace, host.data(), sizeof(ProjVecEntry) * host.size(), hipMemcpyHostToDevice,
+                                  (hipStream_t)stream);
+    if (e != hipSuccess) throw Error(-FKS_EHIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    ProjectMultiArgs a{};
+    a.t = static_cast<const PhxTensor*>(P->dev);
+    a.nt = P->nt;
+    a.partial = reinterpret_cast<double*>(static_cast<uint8_t*>(workspace) + tab_bytes);
+    a.item_lo = lo;
+    a.item_hi = hi;
+    const int grid = project_grid(hi - lo);
+    for (int m0 = 0; m0 < nvec; m0 += kProjMaxVec) {  // batches of vectors over the same seeds
+      a.nvec = std::min(kProjMaxVec, nvec - m0);
+      a.vt = static_cast<const ProjVecEntry*>(workspace) + (size_t)m0 * (size_t)P->nt;
+      for (int s0 = 0; s0 < k; s0 += kPhxSeeds) {
+        const int nb = std::min(kPhxSeeds, k - s0);
+        for (int j = 0; j < nb; j++) a.seeds[j] = seeds[s0 + j];
+        a.nseeds = nb;
+        int rc = timed(0, stream, [&] { return launch_project_multi(a, stream); });
+        if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_multi_kernel launch: ") +
+                                                         (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
+        rc = launch_project_reduce(a.partial, grid, nb, a.nvec, dev_out + (size_t)m0 * (size_t)k + s0, k, stream);
+        if (rc) throw Error(rc < 0 ? rc : -FKS_EHIP, std::string("fks_project_reduce_kernel launch: ") +
+                                                         (rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"));
+      }
     }
   });
 }

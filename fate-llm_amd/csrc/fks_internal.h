@@ -317,7 +317,32 @@ struct ProjectArgs {
 };
 int project_grid(int64_t items);  // workgroups of a launch over `items` work items on the current device
 int launch_project(const ProjectArgs& a, void* stream);
-int launch_project_reduce(const double* partial, int nblocks, int nseeds, double* out, void* stream);
+// fks_project_multi: at most kProjMaxVec vectors share one pass of the generator.  The table
+// is the geometry-only one (base 0: its pointers are not read); vt[m * nt + e] is vector m's
+// piece for table entry e.  Block b leaves partial[b][nvec][kPhxSeeds]; launch_project_reduce
+// adds the blocks in block order into out[m * out_stride + s], m < nvec, s < nseeds.
+constexpr int kProjMaxVec = 4;
+struct ProjVecEntry {
+  uint64_t ptr;     // device address of the entry's first element in the vector
+  int32_t dtype;    // FKS_F32 / FKS_BF16 / FKS_F16, the vector's own
+  uint32_t flags;   // kPhxP16: ptr is 16-byte aligned
+};
+static_assert(sizeof(ProjVecEntry) == 16, "ProjVecEntry layout");
+struct ProjectMultiArgs {
+  uint64_t seeds[kPhxSeeds];
+  const PhxTensor* t;        // sorted by item0
+  const ProjVecEntry* vt;    // [nvec][nt]
+  double* partial;           // [project_grid(item_hi - item_lo)][nvec][kPhxSeeds]
+  int64_t item_lo;
+  int64_t item_hi;
+  int32_t nt;
+  int32_t nseeds;
+  int32_t nvec;
+  int32_t pad;
+};
+int launch_project_multi(const ProjectMultiArgs& a, void* stream);
+int launch_project_reduce(const double* partial, int nblocks, int nseeds, int nvec, double* out, int64_t out_stride,
+                          void* stream);
 
 // launchers (fks_device.hip); return hipError_t as int
 int launch_jump(const JumpArgs& a, int nseeds, void* stream);

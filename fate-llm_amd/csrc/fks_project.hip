@@ -21,6 +21,16 @@
 // partial[block][k], and fks_project_reduce_kernel adds the blocks' partials in block order.
 // The grid is a function of the device and the item range only, so a call's result depends
 // on the device, the tensor list, the shard and the seeds, and on nothing else.
+//
+// fks_project_multi_kernel<NV> (include/fks.h fks_project_multi) is the same walk over NV
+// vectors at once, each read where it lies: the table is the geometry-only one and a second
+// table (ProjVecEntry, [NV][nt]) names every vector's piece per table entry and its dtype
+// (f32, bf16 or f16, widened to f32 exactly when loaded).  Per seed the eight Philox calls
+// and the 32 z are computed once; every vector runs its own fma chain, in fks_project's
+// order, into its own partial, and the reduction carries NV sums per seed (LDS
+// [NV][kProjWaves][kPhxSeeds], partial[block][NV][kPhxSeeds]).  The walk, the seed loop and
+// the block's reduction are templates on NV and on the vector-fetch policy; fks_project_kernel
+// is their NV = 1, one-f32-buffer instance (156 VGPRs, no spill, as before the templates).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +54,24 @@ constexpr int kProjWaves = kProjThreads / 64;
 #ifndef FKS_PROJ_MIN_WAVES   // launch-bounds waves per SIMD (0: none).  4 with FKS_PROJ_LEAN: 147.2 ms; 4 or 5
 #define FKS_PROJ_MIN_WAVES 0 // on the kept form spill to scratch
 #endif
+// fks_project_multi_kernel<NV> (profiles/r10_project_multi_ab.log; same layout, bf16 vectors, against NV launches of
+// the parent build's fks_project_kernel at 122.7 ms each).  The NV x 32 values of a lane stay in registers:
+#ifndef FKS_PROJ_MULTI_CVT_FROM    // vector counts from this one on keep them f32 (32 NV VGPRs) and widen to f64 inside
+#define FKS_PROJ_MULTI_CVT_FROM 3  // the seed loop (an OR with a scalar zero the compiler cannot see through, then the
+#endif                             // conversion); below it the f64 forms are hoisted (64 NV VGPRs).  With the fence:
+                                   // 3 (kept): NV 2 222 VGPRs 0.585, NV 3 192 0.515, NV 4 228 0.436 of NV launches;
+                                   // 2: NV 2 158 VGPRs, three waves per SIMD, but 0.646; never (f64 always): NV 3 and
+                                   // 4 go past 256 VGPRs into AGPR copies at one wave per SIMD, 0.670 and 0.622;
+                                   // per-value "+v" barriers instead of the scalar zero: 40 to 50 VGPRs more
+                                   // (without the fence NV 4 takes 347 registers, 0.635)
+#ifndef FKS_PROJ_MULTI_SCHED_FENCE   // 1: a scheduling barrier after each of a group's eight items, so that one
+#define FKS_PROJ_MULTI_SCHED_FENCE 1 // item's generator is live at a time.  0: NV 3 and 4 need 283 and 268 registers,
+#endif                               // one wave per SIMD (not timed; the f64 forms without it, two-wave bound: NV 4 1.576)
+#ifndef FKS_PROJ_MULTI_MIN_WAVES   // launch-bounds waves per SIMD for NV >= 2.  1 (none): the kept forms hold two
+#define FKS_PROJ_MULTI_MIN_WAVES 1 // waves unforced.  2 on the f64 forms spills to scratch: NV 3 0.539, NV 4 1.448
+#endif
+// Not measured: 2-byte vectors kept packed (16 VGPRs per vector, widened in the loop) and the vectors in LDS
+// (32 KB per f32 vector and workgroup: one workgroup per CU at NV 4, no better than the registers' two waves).
 constexpr int kProjWgPerCu = FKS_PROJ_WG_PER_CU;
 constexpr int kProjLdsTensors = 512;  // tables of at most this many entries are copied to LDS
 constexpr int kProjAccBytes = kProjWaves * kPhxSeeds * 8;  // the waves' sums, in front of the table
@@ -52,6 +80,7 @@ static_assert(kProjAccBytes % 16 == 0, "the LDS table starts 16-byte aligned");
 
 typedef __attribute__((address_space(1))) const u32x4_t proj_gu128;
 typedef __attribute__((address_space(1))) const float proj_gf32;
+typedef __attribute__((address_space(1))) const uint16_t proj_gu16;
 
 // the last table entry whose first item is <= it, at or after lo (items only grow; a wave's
 // next groups lie mostly in the same or the next tensor: a few probes, then bisection)
@@ -97,6 +126,92 @@ __device__ __forceinline__ void proj_load(const PhxTensor& T, uint32_t idx0, uin
     }
 }
 
+// a bf16 / f16 element widened to f32 (exact)
+__device__ __forceinline__ float proj_widen(uint32_t h, bool bf) {
+  const _Float16 f = __builtin_bit_cast(_Float16, (uint16_t)h);
+  return bf ? __uint_as_float(h << 16) : (float)f;
+}
+
+// proj_load for a vector that lies on its own (E: its piece for table entry T, and its
+// dtype): the same 32 elements in the same places.  An f32 vector loads as proj_load does; a
+// 2-byte vector takes one 16-byte load per 8-element run where proj_load takes two; per
+// element where the piece is not 16-byte aligned or the four runs do not lie inside it.
+__device__ __forceinline__ void proj_load_any(const ProjVecEntry& E, const PhxTensor& T, uint32_t idx0, uint64_t j,
+                                              float v[4][kProjVec]) {
+  const int64_t S = (int64_t)T.stride;
+  const int64_t e0 = (int64_t)idx0 + S * (int64_t)(4 * j);
+  const bool whole = (E.flags & kPhxP16) && e0 + 3 * S + kProjVec <= T.numel;
+  if (E.dtype == FKS_F32) {
+    if (whole) {
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        proj_gu128* q = reinterpret_cast<proj_gu128*>(E.ptr + (uint64_t)(e0 + S * i) * 4u);
+        const u32x4_t x = q[0], y = q[1];
+        const uint32_t w[kProjVec] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+#pragma unroll
+        for (int k = 0; k < kProjVec; k++) v[i][k] = __uint_as_float(w[k]);
+      }
+      return;
+    }
+    proj_gf32* p = reinterpret_cast<proj_gf32*>(E.ptr);
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int k = 0; k < kProjVec; k++) {
+        const int64_t e = e0 + S * i + k;
+        v[i][k] = e < T.numel ? p[e] : 0.0f;
+      }
+    return;
+  }
+  const bool bf = E.dtype == FKS_BF16;
+  if (whole) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u32x4_t x = *reinterpret_cast<proj_gu128*>(E.ptr + (uint64_t)(e0 + S * i) * 2u);
+      const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        v[i][2 * k] = proj_widen(w[k] & 0xFFFFu, bf);
+        v[i][2 * k + 1] = proj_widen(w[k] >> 16, bf);
+      }
+    }
+    return;
+  }
+  proj_gu16* p = reinterpret_cast<proj_gu16*>(E.ptr);
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int k = 0; k < kProjVec; k++) {
+      const int64_t e = e0 + S * i + k;
+      v[i][k] = e < T.numel ? proj_widen(p[e], bf) : 0.0f;
+    }
+}
+
+// Vector-fetch policies: where the NV vectors of a pass lie and how a group's elements reach
+// the registers.  ProjFetchBuffer: fks_project's one f32 buffer, which the table entries
+// themselves point into.  ProjFetchTable: fks_project_multi's vectors, each where it lies.
+struct ProjFetchBuffer {
+  static constexpr int NV = 1;
+  __device__ __forceinline__ void load(const PhxTensor& T, int, uint32_t idx0, uint64_t j,
+                                       float v[1][4][kProjVec]) const {
+    proj_load(T, idx0, j, v[0]);
+  }
+};
+template <int N>
+struct ProjFetchTable {
+  static constexpr int NV = N;
+  const ProjVecEntry* vt;  // [NV][nt]
+  int nt;
+  __device__ __forceinline__ void load(const PhxTensor& T, int ti, uint32_t idx0, uint64_t j,
+                                       float v[N][4][kProjVec]) const {
+#pragma unroll
+    for (int m = 0; m < N; m++) {
+      const ProjVecEntry E = vt[(size_t)m * (size_t)nt + (size_t)ti];
+      proj_load_any(E, T, idx0, j, v[m]);
+    }
+  }
+};
+
 __device__ __forceinline__ double proj_wave_sum(double x) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
@@ -105,15 +220,20 @@ __device__ __forceinline__ double proj_wave_sum(double x) {
 
 // Every seed of the pass over the wave's groups whose tensors draw dtype DT (`mine`: this
 // lane has such a group): the whole wave runs this, lanes that are not `mine` enter +0.
-template <int DT>
-__device__ __forceinline__ void proj_seeds(const ProjectArgs& a, uint64_t ctr, uint32_t idx0,
-                                           const float v[4][kProjVec], bool mine, int lane, double& acc) {
+// The z of a seed are drawn once; each of the NV vectors runs its own chain, q then i.
+template <int DT, int NV, bool CVT_IN_LOOP, class Args>
+__device__ __forceinline__ void proj_seeds(const Args& a, uint64_t ctr, uint32_t idx0,
+                                           const float (&v)[NV][4][kProjVec], bool mine, int lane, double (&acc)[NV]) {
   PhxRound1 r1[kProjVec];
 #pragma unroll
   for (int q = 0; q < kProjVec; q++) r1[q] = philox_round1(ctr, idx0 + (uint32_t)q);
   for (int k = 0; k < a.nseeds; k++) {
     const uint64_t seed = a.seeds[k];  // wave-uniform: scalar loads
-    double part = 0.0;
+    uint32_t zero = 0;
+    if constexpr (CVT_IN_LOOP) asm volatile("" : "+s"(zero));  // one opaque scalar per seed
+    double part[NV];
+#pragma unroll
+    for (int m = 0; m < NV; m++) part[m] = 0.0;
 #pragma unroll
     for (int q = 0; q < kProjVec; q++) {
 #if FKS_PROJ_LEAN
@@ -132,22 +252,39 @@ __device__ __forceinline__ void proj_seeds(const ProjectArgs& a, uint64_t ctr, u
         zB = (f32x2_t){phx_cast<DT>(zB.x), phx_cast<DT>(zB.y)};
       }
       // exact products, one rounding per addition
-      float x0 = v[0][q], x1 = v[1][q], x2 = v[2][q], x3 = v[3][q];
+#pragma unroll
+      for (int m = 0; m < NV; m++) {
+        float x0 = v[m][0][q], x1 = v[m][1][q], x2 = v[m][2][q], x3 = v[m][3][q];
 #if FKS_PROJ_LEAN
-      asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));  // opaque: the f64 conversions stay in the loop
+        asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));  // opaque: the f64 conversions stay in the loop
 #endif
-      part = __fma_rn((double)x0, (double)zA.x, part);
-      part = __fma_rn((double)x1, (double)zA.y, part);
-      part = __fma_rn((double)x2, (double)zB.x, part);
-      part = __fma_rn((double)x3, (double)zB.y, part);
+        if constexpr (CVT_IN_LOOP) {  // | 0, a zero the compiler cannot see through: the conversions stay in the loop
+          x0 = __uint_as_float(__float_as_uint(x0) | zero);
+          x1 = __uint_as_float(__float_as_uint(x1) | zero);
+          x2 = __uint_as_float(__float_as_uint(x2) | zero);
+          x3 = __uint_as_float(__float_as_uint(x3) | zero);
+        }
+        part[m] = __fma_rn((double)x0, (double)zA.x, part[m]);
+        part[m] = __fma_rn((double)x1, (double)zA.y, part[m]);
+        part[m] = __fma_rn((double)x2, (double)zB.x, part[m]);
+        part[m] = __fma_rn((double)x3, (double)zB.y, part[m]);
+      }
+#if FKS_PROJ_MULTI_SCHED_FENCE
+      if constexpr (NV > 1) __builtin_amdgcn_sched_barrier(0);  // one item's generator at a time
+#endif
     }
-    const double total = proj_wave_sum(mine ? part : 0.0);
-    acc += lane == k ? total : 0.0;
+#pragma unroll
+    for (int m = 0; m < NV; m++) {
+      const double total = proj_wave_sum(mine ? part[m] : 0.0);
+      acc[m] += lane == k ? total : 0.0;
+    }
   }
 }
 
-template <class Tab>
-__device__ __forceinline__ void proj_walk(const ProjectArgs& a, Tab tab, int lane, double& acc) {
+template <bool CVT_IN_LOOP, class Args, class Tab, class Fetch>
+__device__ __forceinline__ void proj_walk(const Args& a, Tab tab, const Fetch& fetch, int lane,
+                                          double (&acc)[Fetch::NV]) {
+  constexpr int NV = Fetch::NV;
   const int64_t step = (int64_t)gridDim.x * kProjThreads * kProjVec;
   int64_t wb = rfl64(a.item_lo + ((int64_t)blockIdx.x * kProjThreads + (int64_t)(threadIdx.x & ~63u)) * kProjVec);
   int ts = 0;
@@ -164,22 +301,61 @@ __device__ __forceinline__ void proj_walk(const ProjectArgs& a, Tab tab, int lan
     const int64_t r0 = active ? it - T.item0 : 0;
     const uint32_t idx0 = (uint32_t)(r0 % (int64_t)T.stride);
     const uint64_t j = (uint64_t)(r0 / (int64_t)T.stride);
-    float v[4][kProjVec];
+    float v[NV][4][kProjVec];
     if (active) {
-      proj_load(T, idx0, j, v);
+      fetch.load(T, ti, idx0, j, v);
     } else {
 #pragma unroll
-      for (int i = 0; i < 4; i++)
+      for (int m = 0; m < NV; m++)
 #pragma unroll
-        for (int k = 0; k < kProjVec; k++) v[i][k] = 0.0f;
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+          for (int k = 0; k < kProjVec; k++) v[m][i][k] = 0.0f;
     }
     // one pass per dtype present in the wave (wave-uniform branches: a wave lies in one
     // tensor, or in neighbours of one dtype, nearly always)
     const bool m32 = active && T.dtype == FKS_F32, mbf = active && T.dtype == FKS_BF16,
                m16 = active && T.dtype != FKS_F32 && T.dtype != FKS_BF16;
-    if (__any(m32)) proj_seeds<FKS_F32>(a, T.off4 + j, idx0, v, m32, lane, acc);
-    if (__any(mbf)) proj_seeds<FKS_BF16>(a, T.off4 + j, idx0, v, mbf, lane, acc);
-    if (__any(m16)) proj_seeds<FKS_F16>(a, T.off4 + j, idx0, v, m16, lane, acc);
+    if (__any(m32)) proj_seeds<FKS_F32, NV, CVT_IN_LOOP>(a, T.off4 + j, idx0, v, m32, lane, acc);
+    if (__any(mbf)) proj_seeds<FKS_BF16, NV, CVT_IN_LOOP>(a, T.off4 + j, idx0, v, mbf, lane, acc);
+    if (__any(m16)) proj_seeds<FKS_F16, NV, CVT_IN_LOOP>(a, T.off4 + j, idx0, v, m16, lane, acc);
+  }
+}
+
+// One block's part of a pass: the table to LDS (behind the waves' sums), the walk, and the
+// waves' sums added in wave order into partial[block][NV][kPhxSeeds].
+template <bool CVT_IN_LOOP, class Args, class Fetch>
+__device__ __forceinline__ void proj_block(const Args& a, const Fetch& fetch) {
+  constexpr int NV = Fetch::NV;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_proj[];
+  double* s_acc = reinterpret_cast<double*>(s_proj);                              // [NV][kProjWaves][kPhxSeeds]
+  PhxTensor* s_tab = reinterpret_cast<PhxTensor*>(s_proj + NV * kProjAccBytes);
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = (int)(threadIdx.x >> 6);
+  double acc[NV];  // lane k < kPhxSeeds: the wave's sum for seed k, per vector
+#pragma unroll
+  for (int m = 0; m < NV; m++) acc[m] = 0.0;
+  if (a.nt <= kProjLdsTensors) {
+    constexpr int W = (int)(sizeof(PhxTensor) / 4);
+    for (int i = (int)threadIdx.x; i < a.nt * W; i += kProjThreads)
+      reinterpret_cast<uint32_t*>(s_tab)[i] = reinterpret_cast<const uint32_t*>(a.t)[i];
+    __syncthreads();
+    proj_walk<CVT_IN_LOOP>(a, (const PhxTensor*)s_tab, fetch, lane, acc);
+  } else {
+    proj_walk<CVT_IN_LOOP>(a, a.t, fetch, lane, acc);
+  }
+#pragma unroll
+  for (int m = 0; m < NV; m++)
+    if (lane < kPhxSeeds) s_acc[(m * kProjWaves + wave) * kPhxSeeds + lane] = acc[m];
+  __syncthreads();
+  if (threadIdx.x < (unsigned)kPhxSeeds) {
+#pragma unroll
+    for (int m = 0; m < NV; m++) {
+      double s = s_acc[m * kProjWaves * kPhxSeeds + (int)threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < kProjWaves; w++) s += s_acc[(m * kProjWaves + w) * kPhxSeeds + (int)threadIdx.x];
+      a.partial[((size_t)blockIdx.x * NV + m) * kPhxSeeds + threadIdx.x] = s;
+    }
   }
 }
 
@@ -188,39 +364,24 @@ __global__ __launch_bounds__(kProjThreads, FKS_PROJ_MIN_WAVES) void fks_project_
 #else
 __global__ __launch_bounds__(kProjThreads) void fks_project_kernel(ProjectArgs a) {
 #endif
-  extern __shared__ __attribute__((aligned(16))) uint8_t s_proj[];
-  double* s_acc = reinterpret_cast<double*>(s_proj);                              // [kProjWaves][kPhxSeeds]
-  PhxTensor* s_tab = reinterpret_cast<PhxTensor*>(s_proj + kProjAccBytes);
-  const int lane = (int)(threadIdx.x & 63u);
-  const int wave = (int)(threadIdx.x >> 6);
-  double acc = 0.0;  // lane k < kPhxSeeds: the wave's sum for seed k
-  if (a.nt <= kProjLdsTensors) {
-    constexpr int W = (int)(sizeof(PhxTensor) / 4);
-    for (int i = (int)threadIdx.x; i < a.nt * W; i += kProjThreads)
-      reinterpret_cast<uint32_t*>(s_tab)[i] = reinterpret_cast<const uint32_t*>(a.t)[i];
-    __syncthreads();
-    proj_walk(a, (const PhxTensor*)s_tab, lane, acc);
-  } else {
-    proj_walk(a, a.t, lane, acc);
-  }
-  if (lane < kPhxSeeds) s_acc[wave * kPhxSeeds + lane] = acc;
-  __syncthreads();
-  if (threadIdx.x < (unsigned)kPhxSeeds) {
-    double s = s_acc[threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kProjWaves; w++) s += s_acc[w * kPhxSeeds + (int)threadIdx.x];
-    a.partial[(size_t)blockIdx.x * kPhxSeeds + threadIdx.x] = s;
-  }
+  proj_block<false>(a, ProjFetchBuffer{});
 }
 
-// one wave per seed: lane l adds the partials of blocks l, l + 64, ... in order, then the
-// lanes' sums meet in the butterfly
-__global__ __launch_bounds__(64) void fks_project_reduce_kernel(const double* partial, int nblocks, double* out) {
-  const int k = (int)blockIdx.x;
+template <int NV>
+__global__ __launch_bounds__(kProjThreads, NV == 1 ? 1 : FKS_PROJ_MULTI_MIN_WAVES) void fks_project_multi_kernel(
+    ProjectMultiArgs a) {
+  proj_block<(NV >= FKS_PROJ_MULTI_CVT_FROM)>(a, ProjFetchTable<NV>{a.vt, a.nt});
+}
+
+// one wave per (seed, vector): lane l adds the partials of blocks l, l + 64, ... in order,
+// then the lanes' sums meet in the butterfly
+__global__ __launch_bounds__(64) void fks_project_reduce_kernel(const double* partial, int nblocks, double* out,
+                                                                int64_t out_stride) {
+  const int k = (int)blockIdx.x, m = (int)blockIdx.y, nv = (int)gridDim.y;
   double s = 0.0;
-  for (int b = (int)threadIdx.x; b < nblocks; b += 64) s += partial[(size_t)b * kPhxSeeds + k];
+  for (int b = (int)threadIdx.x; b < nblocks; b += 64) s += partial[((size_t)b * nv + m) * kPhxSeeds + k];
   s = proj_wave_sum(s);
-  if (threadIdx.x == 0) out[k] = s;
+  if (threadIdx.x == 0) out[(int64_t)m * out_stride + k] = s;
 }
 
 }  // namespace
@@ -242,10 +403,37 @@ int launch_project(const ProjectArgs& a, void* stream) {
   return (int)hipGetLastError();
 }
 
-int launch_project_reduce(const double* partial, int nblocks, int nseeds, double* out, void* stream) {
-  if (nseeds < 1 || nseeds > kPhxSeeds || nblocks < 1) return -FKS_EINVAL;
-  hipLaunchKernelGGL(fks_project_reduce_kernel, dim3((unsigned)nseeds), dim3(64), 0, (hipStream_t)stream, partial,
-                     nblocks, out);
+namespace {
+template <int NV>
+void project_multi_launch(const ProjectMultiArgs& a, unsigned grid, size_t lds, hipStream_t stream) {
+  hipLaunchKernelGGL(fks_project_multi_kernel<NV>, dim3(grid), dim3(kProjThreads), lds, stream, a);
+}
+}  // namespace
+
+int launch_project_multi(const ProjectMultiArgs& a, void* stream) {
+  static_assert(kProjMaxVec == 4, "one instance per vector count");
+  const int64_t items = a.item_hi - a.item_lo;
+  if (a.nseeds < 1 || a.nseeds > kPhxSeeds || a.nt < 1 || items <= 0 || !a.partial || !a.vt || a.nvec < 1 ||
+      a.nvec > kProjMaxVec)
+    return -FKS_EINVAL;
+  if (a.item_lo % kProjVec != 0 || items % kProjVec != 0) return -FKS_EINVAL;
+  const size_t lds =
+      (size_t)kProjAccBytes * (size_t)a.nvec + (a.nt <= kProjLdsTensors ? sizeof(PhxTensor) * (size_t)a.nt : 0);
+  const unsigned grid = (unsigned)project_grid(items);
+  switch (a.nvec) {
+    case 1: project_multi_launch<1>(a, grid, lds, (hipStream_t)stream); break;
+    case 2: project_multi_launch<2>(a, grid, lds, (hipStream_t)stream); break;
+    case 3: project_multi_launch<3>(a, grid, lds, (hipStream_t)stream); break;
+    default: project_multi_launch<4>(a, grid, lds, (hipStream_t)stream); break;
+  }
+  return (int)hipGetLastError();
+}
+
+int launch_project_reduce(const double* partial, int nblocks, int nseeds, int nvec, double* out, int64_t out_stride,
+                          void* stream) {
+  if (nseeds < 1 || nseeds > kPhxSeeds || nblocks < 1 || nvec < 1 || nvec > kProjMaxVec) return -FKS_EINVAL;
+  hipLaunchKernelGGL(fks_project_reduce_kernel, dim3((unsigned)nseeds, (unsigned)nvec), dim3(64), 0,
+                     (hipStream_t)stream, partial, nblocks, out, out_stride);
   return (int)hipGetLastError();
 }
 

@@ -31,6 +31,7 @@ EXPORTED = (
     "fks_zindex_size", "fks_zindex_attach", "fks_jwin_size", "fks_jwin_size_shard", "fks_jwin_attach",
     "fks_jwin_stats", "fks_cpu_generator_end", "fks_rocm_offset", "fks_rocm_grid_cap", "fks_source_id",
     "fks_digest", "fks_project_workspace_size", "fks_project",
+    "fks_project_multi_workspace_size", "fks_project_multi",
 )
 
 
@@ -44,6 +45,16 @@ class FksTensor(ctypes.Structure):
         ("flags", ctypes.c_uint32),
         ("lr", ctypes.c_float),
         ("wd", ctypes.c_float),
+    ]
+
+
+class FksVec(ctypes.Structure):
+    """struct fks_vec (include/fks.h): one vector's elements for one tensor."""
+
+    _fields_ = [
+        ("data", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -108,6 +119,8 @@ def load():
         L.fks_digest.argtypes = [P, c_i32, c_u64, P, P]
         L.fks_project_workspace_size.argtypes = [P, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_project.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, P, P, c_sz, P]
+        L.fks_project_multi_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_project_multi.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         for name in ("fks_workspace_size", "fks_directional_step", "fks_perturb", "fks_normal",
                      "fks_host_jump_window", "fks_host_tables", "fks_directional_step_shard",
                      "fks_stream_length", "fks_profile_begin", "fks_profile_end", "fks_shard_census", "fks_perturb_step",
@@ -115,7 +128,8 @@ def load():
                      "fks_perturb_step_dev", "fks_device_selfcheck", "fks_zindex_size", "fks_zindex_attach",
                      "fks_jwin_size", "fks_jwin_size_shard", "fks_jwin_attach", "fks_jwin_stats",
                      "fks_cpu_generator_end", "fks_rocm_offset", "fks_rocm_grid_cap", "fks_digest",
-                     "fks_project_workspace_size", "fks_project"):
+                     "fks_project_workspace_size", "fks_project", "fks_project_multi_workspace_size",
+                     "fks_project_multi"):
             getattr(L, name).restype = ctypes.c_int
         if L.fks_abi_version() != ABI_VERSION:
             raise OSError(f"libfks.so ABI {L.fks_abi_version()} != {ABI_VERSION}")

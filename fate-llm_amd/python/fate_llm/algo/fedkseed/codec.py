@@ -642,7 +642,7 @@ def project(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor,
     caller that projects repeatedly should reuse its vec buffer.  An empty tensor for no
     seeds.  Draws nothing from torch's generators
     and leaves them alone.  torch_rocm stream only: a call that resolves to torch_cpu raises
-    NotImplementedError."""
+    NotImplementedError.  ``project_multi`` reads several vectors where they lie, in their own dtype."""
     specs = list(specs)
     device = specs[0].tensor.device if specs else vec.device
     mode = resolve_stream_mode(device, stream_mode)
@@ -669,6 +669,77 @@ def project(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor,
         N.check(L.fks_project(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), vec.data_ptr(), int(shard),
                               int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
     return out  # ws goes back to torch's allocator in stream order
+
+
+def project_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, stream_mode=None,
+                  shard: int = 0, nshards: int = 1) -> torch.Tensor:
+    """``project`` for M vectors at once, each read where it lies (include/fks.h
+    fks_project_multi): out[m, s] = <vectors[m], z_s> over the non-frozen specs' elements that
+    element shard ``shard`` of ``nshards`` owns.  ``vectors`` is a sequence of M sequences with
+    one tensor (or None) per spec.  A tensor that is contiguous, on the specs' device and of
+    float32 / bfloat16 / float16 dtype is read in place, in its own dtype (widened to f32
+    exactly; it need not match the spec's dtype, which still selects z); any other float
+    tensor gets a contiguous f32 copy of that tensor only -- there is no buffer of the model's
+    size.  None stands for a frozen spec's entry only (a frozen spec's tensor is ignored).
+    The z of a seed are drawn once for up to four vectors; row m equals the one-vector call on
+    vectors[m] bit for bit, and a one-vector call on f32 views of one buffer equals
+    ``project`` on that buffer bit for bit.  Returns float64[M, K] on the specs' device,
+    queued on the current stream without synchronisation once the spec list has a cached plan
+    (the plan does not depend on where the vectors live); the vectors are kept alive until the
+    call is queued.  Draws nothing from torch's generators.  torch_rocm stream only: a call
+    that resolves to torch_cpu raises NotImplementedError."""
+    specs = list(specs)
+    vectors = [list(v) for v in vectors]
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: project_multi() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws)")
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    M, n = len(vectors), len(specs)
+    for m, vs in enumerate(vectors):  # every argument error before anything touches a device
+        if len(vs) != n:
+            raise ValueError(f"vector {m}: one tensor per spec is needed: {n} specs, {len(vs)} tensors")
+        for i, (sp, v) in enumerate(zip(specs, vs)):
+            if sp.frozen:
+                continue  # ignored
+            if v is None:
+                raise ValueError(f"vector {m}: spec {i} is not frozen and has no tensor")
+            if not v.is_floating_point() or v.numel() != sp.tensor.numel():
+                raise ValueError(f"vector {m}, spec {i}: a floating-point tensor of {sp.tensor.numel()} elements is "
+                                 f"needed, got {v.dtype} {tuple(v.shape)}")
+            if v.device != sp.tensor.device:
+                raise ValueError(f"vector {m}, spec {i}: on {v.device}, the spec is on {sp.tensor.device}")
+    b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    s = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    varr = (N.FksVec * max(1, M * n))()
+    keep = []  # the tensors the call reads (the copies among them live nowhere else)
+    for m, vs in enumerate(vectors):
+        for i, (sp, v) in enumerate(zip(specs, vs)):
+            if sp.frozen:
+                continue  # a NULL entry
+            v = v.detach()
+            if v.dtype not in _DTYPES or not v.is_contiguous():
+                v = v.to(torch.float32).contiguous()
+            keep.append(v)
+            varr[m * n + i].data = v.data_ptr() if v.numel() else None
+            varr[m * n + i].dtype = _DTYPES[v.dtype]
+    if b.device is None:  # no spec at all
+        return torch.zeros((M, len(s)), dtype=torch.float64)
+    out = torch.empty((M, len(s)), dtype=torch.float64, device=b.device)
+    if not out.numel():
+        return out
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_project_multi_workspace_size(ctypes.addressof(b.arr), b.n, len(s), M, ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_project_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), ctypes.addressof(varr), M,
+                                    int(shard), int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
+                                    _stream_handle(b.device)))
+    del keep  # queued: the copies and ws go back to torch's allocator in stream order
+    return out
 
 
 # ---------------------------------------------------------------- model fingerprint (FKSD-1)

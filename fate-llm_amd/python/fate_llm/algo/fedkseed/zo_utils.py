@@ -227,7 +227,8 @@ def seed_projections(param_groups: List[dict], seeds: Sequence[int], vectors=Non
     model's size, so its first launch also builds the buffer's tensor table (an allocation and
     a synchronous upload; codec.project).  Returns float64[K] on the parameters' device,
     queued on the current stream (codec.project: exact products, f64 sums, bit-reproducible;
-    torch_rocm stream only).  torch's generators are left alone."""
+    torch_rocm stream only).  torch's generators are left alone.
+    ``seed_projections_multi`` reads the vectors in place, in their own dtype, several per pass."""
     specs, vec, _ = _projection_inputs(param_groups, vectors)
     if vec is None:
         return torch.zeros(len(seeds), dtype=torch.float64)
@@ -244,11 +245,55 @@ def fit_seed_scalars(param_groups: List[dict], seeds: Sequence[int], delta_vecto
     diagonal deviates from N by O(sqrt(2 N)), its off-diagonal entries are O(sqrt(N)) --, so
     these scalars differ from the least-squares ones by a relative error of order
     sqrt(K / N): negligible for K << N.  What is fitted is the projection of delta on the
-    K-seed subspace, a share of about K / N of a generic delta's energy."""
+    K-seed subspace, a share of about K / N of a generic delta's energy.
+    ``fit_seed_scalars_multi`` fits several deltas in one pass, each read in place."""
     specs, vec, n_live = _projection_inputs(param_groups, delta_vectors)
     if vec is None or n_live == 0:
         raise ValueError("fit_seed_scalars: no parameter requires grad")
     return codec.project(specs, seeds, vec, stream_mode=stream_mode) / float(n_live)
+
+
+def _projection_specs(param_groups: List[dict], vector_lists):
+    """(specs, vector lists, N) of the in-place forms: no buffer is built, codec.project_multi
+    reads every tensor where it lies."""
+    params = [p for g in param_groups for p in g["params"]]
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    if vector_lists is None:
+        for i, p in enumerate(params):
+            if p.requires_grad and p.grad is None:
+                raise ValueError(f"parameter {i} requires grad and has no vector (its .grad is None)")
+        vector_lists = [[p.grad if p.requires_grad else None for p in params]]
+    vector_lists = [list(vs) for vs in vector_lists]
+    for m, vs in enumerate(vector_lists):
+        if len(vs) != len(params):
+            raise ValueError(f"vector list {m}: one vector per parameter: {len(params)} parameters, {len(vs)} vectors")
+    return specs, vector_lists, sum(p.numel() for p in params if p.requires_grad)
+
+
+def seed_projections_multi(param_groups: List[dict], seeds: Sequence[int], vector_lists=None,
+                           stream_mode=None) -> torch.Tensor:
+    """``seed_projections`` of M vector lists in one call, float64[M, K]: every vector is read
+    where it lies, in its own dtype (a bf16 model's ``.grad``s as bf16: no f32 buffer of the
+    model's size, no conversion pass), and up to four lists share each pass of the generator
+    (codec.project_multi).  ``vector_lists``: M lists with one tensor per parameter (None for
+    a parameter that does not require grad); default: one list, every parameter's ``.grad``,
+    and a [1, K] result.  Row m equals the one-list call on list m bit for bit, and equals
+    ``seed_projections`` of the same vectors bit for bit."""
+    specs, vector_lists, _ = _projection_specs(param_groups, vector_lists)
+    if not specs:
+        return torch.zeros((len(vector_lists), len(seeds)), dtype=torch.float64)
+    return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode)
+
+
+def fit_seed_scalars_multi(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                           stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars`` of M dense deltas in one call: ``seed_projections_multi / N``,
+    float64[M, K] -- an arbiter turning the deltas of several first-order or FedAvg parties
+    into (seed, scalar) form pays for one pass of the generator per four parties."""
+    specs, vector_lists, n_live = _projection_specs(param_groups, delta_vector_lists)
+    if not specs or n_live == 0:
+        raise ValueError("fit_seed_scalars_multi: no parameter requires grad")
+    return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode) / float(n_live)
 
 
 def build_seed_candidates(k, low=0, high=2**32):

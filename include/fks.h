@@ -303,6 +303,43 @@ int fks_project_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, size_
 int fks_project(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
                 int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- seed-basis projection of several vectors, each read where it lies ----
+ * fks_project_multi: dev_out[m * k + s] = sum over the non-frozen tensors i and the elements e
+ * that element shard `shard` of `nshards` owns of (double)f32(vecs[m * nt + i][e]) *
+ * (double)z_s(i, e), m < nvec, s < k.  vecs is a HOST array of nvec x nt entries;
+ * vecs[m * nt + i].data is a DEVICE pointer to t[i].numel contiguous elements of
+ * vecs[m * nt + i].dtype (FKS_F32, FKS_BF16 or FKS_F16), aligned to its element size only.  A
+ * vector's dtype is independent of the tensor's, which still selects z; a bf16 or f16 element
+ * is widened to f32 exactly, so every product stays exact in f64.  Entries of frozen and empty
+ * tensors are ignored and may be NULL; frozen tensors still advance the Philox offset.  No
+ * model-size staging buffer exists anywhere: the gradients of a bf16 model are read as bf16.
+ * At most 4 vectors share one pass of the generator (the z of a seed are drawn once for all of
+ * them); a larger nvec runs in batches of 4 over the same seeds, seeds in passes of 32.
+ * The additions run in fks_project's order (the same grid, groups and fma chain per vector,
+ * then wave butterfly, waves in wave order, blocks in block order; no floating-point atomic):
+ *   - row m of a call with nvec vectors equals the nvec == 1 call on vector m, bit for bit;
+ *   - a one-vector call whose entries are f32 and lie end to end in one 8-byte aligned buffer
+ *     equals fks_project on that buffer, bit for bit.
+ * So a result depends neither on how the caller batches its vectors nor on the alignment of
+ * any of them.  dev_out (nvec * k doubles, device memory, 8-byte aligned) is OVERWRITTEN in
+ * stream order, never accumulated into.  The tensors' data pointers are not read and the
+ * vectors' addresses key no cached plan: the per-call table of vector pointers travels in the
+ * workspace, uploaded in stream order.  k == 0, nvec == 0, nt == 0 and all-empty lists
+ * succeed; a shard with no element zeroes its nvec * k outputs.  Workspace:
+ * fks_project_multi_workspace_size (8-byte aligned).  Errors, raised from the arguments alone
+ * before any device work: nvec < 0, a NULL vecs with nvec > 0 and nt > 0, a vector dtype
+ * outside the three, a NULL or misaligned vector pointer for a non-frozen, non-empty tensor, a
+ * NULL or misaligned dev_out with k > 0 and nvec > 0, a bad shard, too small or misaligned a
+ * workspace: -FKS_EINVAL; tensors of the CPU generator's stream: -FKS_ENOTSUP.            */
+typedef struct fks_vec {
+  const void* data; /* device pointer: the vector's elements for one tensor */
+  int32_t dtype;    /* FKS_F32 / FKS_BF16 / FKS_F16 */
+  int32_t reserved; /* 0 */
+} fks_vec;
+int fks_project_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
+int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs, int32_t nvec,
+                      int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
