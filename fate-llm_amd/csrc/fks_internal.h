@@ -12,7 +12,7 @@
 
 namespace fks {
 
-// Exceptions never cross the C ABI: fks_capi.cpp converts them to codes.
+// Exceptions never cross the C ABI: fks_capi.cpp (guarded) converts them to codes.
 struct Error : std::runtime_error {
   int code;
   Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
@@ -98,7 +98,7 @@ constexpr int kSmallWgPerCu = 8;
 constexpr int kSm2ZidxPerBlock = 156;
 constexpr int kSm2ZidxBytesPerBlock = 4 * kSm2ZidxPerBlock;
 constexpr int kJumpThreads = 1024;  // 16 waves, one chunk's jump per wave at a time
-constexpr int kJumpMaxCpw = 32;  // most chunks one jump workgroup takes (fks_capi.cpp jump_chunks_per_wg)
+constexpr int kJumpMaxCpw = 32;  // most chunks one jump workgroup takes (fks_run.cpp jump_chunks_per_wg)
 constexpr int kJumpXLen = 19937 + 624;  // x[0..20560]: y[i + w] = x[i + w + 1], i < 19937, w < 624
 
 // kModeUpdateWd / kModeUpdateNoWd: kModeUpdate specialised for a launch whose segments
@@ -134,7 +134,7 @@ enum ApplyMode : int {
 
 // Per-pass seeds and multipliers travel BY VALUE in the kernel arguments: a call
 // uploads nothing per pass, and the static header (chunk table, jump polynomials,
-// descriptors) is cached on the device across calls (fks_capi.cpp, PlanCache).
+// descriptors) is cached on the device across calls (fks_cache.cpp, get_plan).
 struct ApplyArgs {
   const uint32_t* states;       // [nseeds][nchunks][624] generator windows at chunk starts
   float g[kMaxSeedsPerPass];    // update multiplier per seed (mode 0) / delta coefficient

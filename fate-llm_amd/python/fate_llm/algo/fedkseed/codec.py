@@ -409,7 +409,7 @@ def zindex_release(device=None) -> None:
 # round, so from the second round on the jumps are skipped.  A torch tensor taken under
 # JWIN_BUDGET_FRAC of the device's memory and never past its free memory (less
 # ZINDEX_HEADROOM); an allocation failure only means "jump"; FKS_NO_JWIN=1 (or true / yes)
-# turns it off, as FKS_NO_JWIN does in the library (fks_capi.cpp env_on).
+# turns it off, as FKS_NO_JWIN does in the library (fks_cache.cpp env_on).
 JWIN_BUDGET_FRAC = float(os.environ.get("FKS_JWIN_BUDGET_FRAC", "0.05"))
 _jwin = {}  # device index -> attached uint8 tensor
 

@@ -180,7 +180,7 @@ def test_seed_sharded_reconstruct_leaves_the_generators():
 
 
 def test_grid_cap_is_torchs():
-    """The grid cap the library draws with (fks_capi.cpp phx_geometry) and carries on the
+    """The grid cap the library draws with (fks_phx.cpp phx_geometry) and carries on the
     wire is the one torch's calc_execution_policy derives (DistributionTemplates.h:55-57)
     from the device properties; and a tensor of exactly 256 x cap x 4 + 1 elements -- one
     past a single loop iteration of the full grid -- draws torch's values."""

@@ -6,7 +6,7 @@ increment, then -- when the iterator cannot use 32-bit indexing (largest byte of
 INT32_MAX) -- draws each piece TensorIterator::with_32bit_indexing yields (halves split until
 they fit: first floor(n / 2) elements then the rest, recursively) as a call of its own, with
 its own launch geometry and its own reservation; the intermediate halves reserve nothing
-(the 4.4 GB case, four pieces, pins that).  fks_capi.cpp phx_geometry restates that: each piece is a table
+(the 4.4 GB case, four pieces, pins that).  fks_phx.cpp phx_geometry restates that: each piece is a table
 entry of its own.  Oracle: torch.normal(device="cuda") itself, and the reference's update
 expression as torch ops on the device (oracle/torch_replica.py).  Bar: bit-exact, and the
 device generator's offset after the call equal to torch's.

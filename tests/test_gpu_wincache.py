@@ -1,4 +1,4 @@
-"""The one-seed caches (fks_capi.cpp): the jumped-window cache (WinCache) and the bf16
+"""The one-seed caches (fks_cache.cpp): the jumped-window cache (WinCache) and the bf16
 z-index cache (ZCache: a perturb stores every block's table indices, later calls with
 the same seed replay them without the generator).  A sequence of perturb / perturb_step
 / K=1 update calls that hits, misses (new seed, other tensor list with other chunk
