@@ -188,6 +188,37 @@ int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, in
   });
 }
 
+// ---- seed-basis projection (CPU generator's stream) ----
+static void project_mt_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_project_mt: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_project is the call for that stream");
+}
+
+int fks_project_mt_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    project_mt_check_stream(t, nt);
+    *bytes = project_mt_ws(t, nt, k, 0, 1, device_cu_count()).total;
+  });
+}
+
+int fks_project_mt(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
+                   int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    check_shard(shard, nshards);
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (k > 0 && (!vec || ((uintptr_t)vec % 8) != 0)) throw Error(-FKS_EINVAL, "null or misaligned vector");
+    if (k > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned projection output");
+    project_mt_check_stream(t, nt);
+    if (k == 0) return;
+    project_mt(t, nt, seeds, k, vec, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
 int fks_directional_step(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* values, int32_t k,
                          int32_t value_kind, void* workspace, size_t ws_bytes, void* stream) {
   return guarded([&] { run(t, nt, seeds, values, k, value_kind, kModeUpdate, workspace, ws_bytes, stream); });

@@ -101,6 +101,13 @@ PlanImage plan_image(const fks_tensor* t, int nt, const double* scales, uint64_t
 constexpr size_t kWsStatesOff = 4096;
 size_t ws_bytes_for(int chunks, int seeds_per_pass);
 size_t workspace_total(const fks_tensor* t, int nt, int k, uint64_t delta_base, int cus);
+// fks_project_mt's workspace for one shard's plan (bounds; shard 0 of 1 bounds every shard)
+struct ProjMtWs {
+  size_t partial_off = 0, total = 0;  // where the partial rows start; bytes in all
+  int rows = 0;                       // partial rows of one pass, at most
+  bool work = false;                  // the shard holds an element of a non-frozen tensor
+};
+ProjMtWs project_mt_ws(const fks_tensor* t, int nt, int k, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -279,5 +286,8 @@ void device_selfcheck(int which, uint64_t* result, void* workspace, size_t ws_by
 size_t project_ws_bytes(const fks_tensor* t, int nt, int nvec, bool multi);
 void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, const fks_vec* vecs,
              int nvec, int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_project_mt: the same projection on the CPU generator's stream (the kModeDelta plan of vec)
+void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
+                double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 
 }  // namespace fks

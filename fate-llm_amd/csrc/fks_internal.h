@@ -344,6 +344,39 @@ int launch_project_multi(const ProjectMultiArgs& a, void* stream);
 int launch_project_reduce(const double* partial, int nblocks, int nseeds, int nvec, double* out, int64_t out_stride,
                           void* stream);
 
+// ---- seed-basis projection on the CPU generator's stream (fks_project_mt.hip) ----
+// One pass of at most kMaxSeedsPerPass seeds over a kModeDelta plan (the descriptors point into
+// the f32 vector): the workgroup of chunk c leaves its per-seed f64 sums in partial[c][kPhxSeeds].
+// The launches of a pass -- one per dtype with fast segments, then the irregular one -- lay their
+// rows one after another and launch_project_reduce adds them in row order.
+struct ProjMtArgs {
+  const uint32_t* states;       // [nseeds][nchunks][624] generator windows at chunk starts
+  const DevSeg* segs;           // fast segments of this launch's dtype, sorted by start
+  const int64_t* chunk_block;   // [nchunks + 1] first MT block of each chunk
+  const uint64_t* sink;         // 4 KB of workspace: what lanes off every segment load (never summed)
+  double* partial;              // [nchunks][kPhxSeeds]
+  int32_t nsegs;
+  int32_t nchunks;
+  int32_t nseeds;
+  int32_t pad;
+};
+struct ProjMtIrrArgs {
+  const uint32_t* states;       // [nseeds][nchunks][624]
+  const DevRun* runs;           // sorted by start (disjoint)
+  const DevTiny* tiny;          // sorted by word
+  const int64_t* chunk_lo;      // [nchunks] chunk c twists MT blocks [chunk_lo[c], chunk_hi[c])
+  const int64_t* chunk_hi;
+  double* partial;              // [nchunks][kPhxSeeds]
+  int32_t nruns;
+  int32_t ntiny;
+  int32_t nchunks;
+  int32_t nseeds;
+  int32_t libm;                 // fp32 runs draw the libm flavour (FKS_LIBM: kDtF32Libm)
+  int32_t pad;
+};
+int launch_project_mt(int dtype, const ProjMtArgs& a, void* stream);  // dtype: FKS_F32, FKS_BF16 or kDtF32Libm
+int launch_project_mt_irr(const ProjMtIrrArgs& a, void* stream);
+
 // launchers (fks_device.hip); return hipError_t as int
 int launch_jump(const JumpArgs& a, int nseeds, void* stream);
 int launch_apply(int dtype, const ApplyArgs& a, void* stream);

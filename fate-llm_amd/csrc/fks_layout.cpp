@@ -279,6 +279,28 @@ size_t workspace_total(const fks_tensor* t, int nt, int k, uint64_t delta_base, 
   return bytes;
 }
 
+// fks_project_mt's workspace: [sink 4 KB | generator windows of one pass | partial rows], the
+// rows of a pass's launches -- one per dtype with fast segments, then the irregular one -- one
+// after another.  Bounds of what shard `shard`'s plan launches; the whole list's (shard 0 of 1)
+// bound every shard's, since each term grows with the blocks a shard holds.
+ProjMtWs project_mt_ws(const fks_tensor* t, int nt, int k, int shard, int nshards, int cus) {
+  Layout L = make_layout(t, nt, nullptr, 256);  // any 8-byte aligned base gives the same layout
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  ProjMtWs w;
+  int reg = 0, ndt = 0;
+  for (int d = 0; d < 3; d++) ndt += L.segs[d].empty() ? 0 : 1;
+  if (ndt) reg = plan_nchunks(std::max<int64_t>(1, br.hi - br.lo), false, cus);
+  int64_t covered = 0;  // owner blocks of the irregular work
+  for (auto& x : irregular_owner_intervals(L)) covered += x.second - x.first;
+  const int irr = covered ? plan_nchunks(covered, false, cus) : 0;
+  w.work = ndt > 0 || irr > 0;
+  w.rows = ndt * reg + irr;
+  w.partial_off = align_up(ws_bytes_for(std::max(reg, irr), std::max(1, std::min(k, kMaxSeedsPerPass))), 256);
+  w.total = w.partial_off + sizeof(double) * (size_t)kPhxSeeds * (size_t)std::max(w.rows, 1);
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

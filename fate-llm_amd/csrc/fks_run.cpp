@@ -523,4 +523,81 @@ void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fl
   }
 }
 
+// ---- seed-basis projection (CPU generator's stream) ----
+// The plan fks_delta_accumulate launches for `vec` as its delta buffer; per pass of
+// kMaxSeedsPerPass seeds the regular jump, one launch per dtype with fast segments, the irregular
+// jump and launch, then the reduce over the rows all of them left.  No window, z-index or
+// reconstruct-window cache: the workspace holds the windows, the sink and the partial rows.
+void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
+                double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  // the layout on the host first: the workspace is checked before anything is allocated or launched
+  const DevCaps dc = device_caps();
+  const ProjMtWs W = project_mt_ws(t, nt, k, shard, nshards, dc.cus);
+  if (!W.work) {  // nothing in this shard: every projection is +0
+    check_hip(hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)k, (hipStream_t)stream), "hipMemsetAsync");
+    return;
+  }
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < W.total)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(W.total) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, (uint64_t)(uintptr_t)vec, shard, nshards, /*small=*/false, dc);
+  int rows = C->have_irr ? C->Z.irr_chunks : 0;
+  for (int d = 0; d < 3; d++) rows += C->nsegs[d] ? C->Z.reg_chunks : 0;
+  if (rows < 1 || rows > W.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.partial_off)
+    throw Error(-FKS_EINVAL, "the plan does not match the call's workspace layout");
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  double* const partial = reinterpret_cast<double*>(ws + W.partial_off);
+  for (int s0 = 0; s0 < k; s0 += kMaxSeedsPerPass) {
+    const int nb = std::min(kMaxSeedsPerPass, k - s0);
+    double* row = partial;
+    if (C->have_reg) {
+      JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_polys, C->H.off_cb, states, C->Z.reg_chunks);
+      ja.chunks_per_wg = jump_chunks_per_wg(nb, C->Z.reg_chunks, dc.cus);
+      check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+      for (int d = 0; d < 3; d++) {
+        if (!C->nsegs[d]) continue;
+        ProjMtArgs pa{};
+        pa.states = states;
+        pa.segs = reinterpret_cast<const DevSeg*>(hdr + C->seg_off[d]);
+        pa.chunk_block = ja.chunk_block;
+        pa.sink = reinterpret_cast<const uint64_t*>(ws);
+        pa.partial = row;
+        pa.nsegs = C->nsegs[d];
+        pa.nchunks = C->Z.reg_chunks;
+        pa.nseeds = nb;
+        const int dd = (d == FKS_F32 && libm) ? kDtF32Libm : d;
+        check_launch(timed(0, stream, [&] { return launch_project_mt(dd, pa, stream); }), "fks_project_mt_kernel",
+                     "bad arguments");
+        row += (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+      }
+    }
+    if (C->have_irr) {
+      JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_ipolys, C->H.off_ilo, states, C->Z.irr_chunks);
+      ja.chunks_per_wg = std::max(1, std::min(32, C->Z.irr_chunks));
+      check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+      ProjMtIrrArgs ia{};
+      ia.states = states;
+      ia.runs = reinterpret_cast<const DevRun*>(hdr + C->H.off_runs);
+      ia.tiny = reinterpret_cast<const DevTiny*>(hdr + C->H.off_tiny);
+      ia.chunk_lo = ja.chunk_block;
+      ia.chunk_hi = reinterpret_cast<const int64_t*>(hdr + C->H.off_ihi);
+      ia.partial = row;
+      ia.nruns = C->Z.nruns;
+      ia.ntiny = C->Z.ntiny;
+      ia.nchunks = C->Z.irr_chunks;
+      ia.nseeds = nb;
+      ia.libm = libm ? 1 : 0;
+      check_launch(timed(0, stream, [&] { return launch_project_mt_irr(ia, stream); }), "fks_project_mt_irr_kernel",
+                   "bad arguments");
+    }
+    check_launch(launch_project_reduce(partial, rows, nb, 1, dev_out + s0, 0, stream), "fks_project_reduce_kernel",
+                 "bad arguments");
+  }
+}
+
 }  // namespace fks

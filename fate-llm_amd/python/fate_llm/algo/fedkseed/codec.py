@@ -642,7 +642,8 @@ def project(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor,
     caller that projects repeatedly should reuse its vec buffer.  An empty tensor for no
     seeds.  Draws nothing from torch's generators
     and leaves them alone.  torch_rocm stream only: a call that resolves to torch_cpu raises
-    NotImplementedError.  ``project_multi`` reads several vectors where they lie, in their own dtype."""
+    NotImplementedError (``project_mt`` is that stream's call; ``zo_utils.seed_projections`` picks
+    between the two).  ``project_multi`` reads several vectors where they lie, in their own dtype."""
     specs = list(specs)
     device = specs[0].tensor.device if specs else vec.device
     mode = resolve_stream_mode(device, stream_mode)
@@ -668,6 +669,45 @@ def project(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor,
         ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
         N.check(L.fks_project(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), vec.data_ptr(), int(shard),
                               int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    return out  # ws goes back to torch's allocator in stream order
+
+
+def project_mt(specs: Sequence[ParamSpec], seeds: Sequence[int], vec: torch.Tensor, shard: int = 0,
+               nshards: int = 1) -> torch.Tensor:
+    """``project`` on the torch_cpu stream (include/fks.h fks_project_mt), the adjoint of
+    ``delta_accumulate(..., stream_mode="torch_cpu")``: out[s] = <vec, z_s> over the non-frozen
+    specs' elements that element shard ``shard`` of ``nshards`` owns
+    (``shard_range(..., stream_mode="torch_cpu")``; the shards' results add up to the whole
+    call's), z_s the CPU generator's MT19937 draw for seeds[s] in each spec's dtype -- fp32 in
+    the process's flavour (``cpu_fp32_flavour``), as every CPU-stream call.  ``vec`` is the f32
+    concatenation of the specs' elements (frozen specs keep their range, draw and contribute
+    nothing; their range is not read).  It takes no ``stream_mode``: the stream is always
+    torch_cpu.  Exact products, f64 sums in one fixed order: the same call gives the same bits,
+    wherever vec lies.  Returns a float64[K] tensor on the specs' device, queued on the current
+    stream; as with ``project``, the first call with a vec at a new address builds and uploads
+    the plan, so a caller that projects repeatedly should reuse its vec buffer.  An empty
+    tensor for no seeds.  Draws nothing from torch's generators and leaves them alone."""
+    specs = list(specs)
+    b = _Batch(specs, "torch_cpu", stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    if b.device is None:
+        b.device = vec.device
+    _check_delta(b, vec)
+    s = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    out = torch.empty(len(s), dtype=torch.float64, device=b.device)
+    if not len(s):
+        return out
+    if not vec.numel():  # no element anywhere: every projection is +0
+        return out.zero_()
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_project_mt_workspace_size(ctypes.addressof(b.arr), b.n, len(s), ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_project_mt(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), vec.data_ptr(), int(shard),
+                                 int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
+                                 _stream_handle(b.device)))
     return out  # ws goes back to torch's allocator in stream order
 
 

@@ -206,6 +206,14 @@ def _projection_inputs(param_groups: List[dict], vectors):
     return specs, vec, n_live
 
 
+def _project_on_stream(specs, seeds, vec, stream_mode):
+    """codec.project on the torch_rocm stream, codec.project_mt on torch_cpu: the stream the
+    call resolves to on the vector's device."""
+    if codec.resolve_stream_mode(vec.device, stream_mode) == "torch_cpu":
+        return codec.project_mt(specs, seeds, vec)
+    return codec.project(specs, seeds, vec, stream_mode=stream_mode)
+
+
 def seed_projections(param_groups: List[dict], seeds: Sequence[int], vectors=None, stream_mode=None) -> torch.Tensor:
     """g_k = <v, z_k> for every seed: the exact directional derivatives of the K seed
     candidates along a dense vector -- with v the gradient, one backward pass instead of two
@@ -226,13 +234,15 @@ def seed_projections(param_groups: List[dict], seeds: Sequence[int], vectors=Non
     The vectors are read as f32, and each call lays them out in a new f32 buffer of the
     model's size, so its first launch also builds the buffer's tensor table (an allocation and
     a synchronous upload; codec.project).  Returns float64[K] on the parameters' device,
-    queued on the current stream (codec.project: exact products, f64 sums, bit-reproducible;
-    torch_rocm stream only).  torch's generators are left alone.
-    ``seed_projections_multi`` reads the vectors in place, in their own dtype, several per pass."""
+    queued on the current stream (exact products, f64 sums, bit-reproducible), on either stream:
+    a call that resolves to torch_rocm takes codec.project, one that resolves to torch_cpu
+    codec.project_mt.  torch's generators are left alone.
+    ``seed_projections_multi`` reads the vectors in place, in their own dtype, several per pass
+    (torch_rocm stream only)."""
     specs, vec, _ = _projection_inputs(param_groups, vectors)
     if vec is None:
         return torch.zeros(len(seeds), dtype=torch.float64)
-    return codec.project(specs, seeds, vec, stream_mode=stream_mode)
+    return _project_on_stream(specs, seeds, vec, stream_mode)
 
 
 def fit_seed_scalars(param_groups: List[dict], seeds: Sequence[int], delta_vectors, stream_mode=None) -> torch.Tensor:
@@ -245,12 +255,13 @@ def fit_seed_scalars(param_groups: List[dict], seeds: Sequence[int], delta_vecto
     diagonal deviates from N by O(sqrt(2 N)), its off-diagonal entries are O(sqrt(N)) --, so
     these scalars differ from the least-squares ones by a relative error of order
     sqrt(K / N): negligible for K << N.  What is fitted is the projection of delta on the
-    K-seed subspace, a share of about K / N of a generic delta's energy.
-    ``fit_seed_scalars_multi`` fits several deltas in one pass, each read in place."""
+    K-seed subspace, a share of about K / N of a generic delta's energy.  Either stream, as
+    ``seed_projections``.
+    ``fit_seed_scalars_multi`` fits several deltas in one pass, each read in place (torch_rocm only)."""
     specs, vec, n_live = _projection_inputs(param_groups, delta_vectors)
     if vec is None or n_live == 0:
         raise ValueError("fit_seed_scalars: no parameter requires grad")
-    return codec.project(specs, seeds, vec, stream_mode=stream_mode) / float(n_live)
+    return _project_on_stream(specs, seeds, vec, stream_mode) / float(n_live)
 
 
 def _projection_specs(param_groups: List[dict], vector_lists):

@@ -272,7 +272,7 @@ int fks_delta_accumulate(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
 int fks_delta_apply(const fks_tensor* t, int32_t nt, const float* delta, const double* decay, void* workspace,
                     size_t ws_bytes, void* stream);
 
-/* ---- seed-basis projection: g_s = <v, z_s> (FKS_STREAM_ROCM only) ----
+/* ---- seed-basis projection: g_s = <v, z_s> (FKS_STREAM_ROCM; fks_project_mt below: MT19937) ----
  * The adjoint of fks_delta_accumulate (delta = Z c): a dense f32 vector expressed in the K
  * seeds, Z^T v.  With v = grad f these are the exact directional derivatives of all K
  * candidates from one backward pass -- the wire's own K scalars (fedkseed.py:136-141 applies
@@ -339,6 +339,36 @@ typedef struct fks_vec {
 int fks_project_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
 int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs, int32_t nvec,
                       int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- seed-basis projection on the CPU generator's stream (MT19937) ----
+ * fks_project_mt: fks_project's contract on the other stream.  dev_out[s] = sum over the
+ * non-frozen tensors i and the elements e that element shard `shard` of `nshards` owns of
+ * (double)vec[cum_i + e] * (double)z_s(i, e), s < k; vec follows fks_delta_accumulate's buffer
+ * (f32, device memory, 8-byte aligned, the tensors' concatenation; frozen and empty tensors keep
+ * their range, and a frozen tensor's range is never read).  z_s is the value fks_normal writes
+ * for seeds[s] on the CPU generator's stream in the tensor's dtype: the FKS_LIBM flavour for
+ * fp32 where the list carries it, the ragged head and the 16-word tail recompute, the serial
+ * numel < 16 draws with their cached second value; frozen tensors advance the stream and
+ * contribute nothing.  The shards are fks_directional_step_shard's runs of whole MT blocks
+ * (fks_shard_census); the shards' results add up to the whole call's.  Every product is exact
+ * in f64 and the additions are f64 in ONE fixed order, with no floating-point atomic: per seed a
+ * lane's fma chain over its elements of a plan chunk, a 64-lane butterfly, the workgroup's waves
+ * in wave order, then the chunks' rows of the pass's launches (one per dtype with 16-aligned
+ * segments, then the irregular one) in row order.  The result is bit-reproducible for the same
+ * device, tensor list, shard and seeds, whatever 8-byte aligned address vec has; the error of
+ * any f64 order is at most n 2^-52 sum |v z| over the n terms.  dev_out (k doubles, device
+ * memory, 8-byte aligned) is OVERWRITTEN in stream order, never accumulated into; seeds go in
+ * passes of 19.  lr, wd and the other flags are ignored; the tensors' data pointers are not
+ * read.  Draws nothing from torch's generators.  k == 0, nt == 0 and all-empty lists succeed;
+ * k > 0 with no element in the shard zeroes dev_out.  Workspace: fks_project_mt_workspace_size
+ * (8-byte aligned; a function of the list, k and the device alone).  Errors, raised from the
+ * arguments alone before any device work: null or misaligned vec / dev_out with k > 0, a bad
+ * shard, null seeds with k > 0, k < 0, a workspace that is null, misaligned or too small:
+ * -FKS_EINVAL; a list that carries FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_project is the call for
+ * that stream).                                                                            */
+int fks_project_mt_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, size_t* bytes);
+int fks_project_mt(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
+                   int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
