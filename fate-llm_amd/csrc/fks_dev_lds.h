@@ -15,6 +15,13 @@ __device__ __forceinline__ uint32_t swap_adjacent(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
 }
 
+// sum of x over the 64 lanes of the wave, in every lane: the xor butterfly, one fixed order
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+
 // ------------------------------------------------------------------ LDS accessors
 // LDS accessors by byte offset.  The apply kernel's only LDS is its dynamic block,
 // which starts at LDS address 0 (no static __shared__; checked at kernel entry), so an

@@ -27,6 +27,23 @@ constexpr int kLdsTabBytes = kLdsRBytes + 256 * 8;
 constexpr int kLdsCsOff = kLdsRBytes;
 constexpr int kLdsStBytes = (kMaxSeedsPerPass + 1) * kMtN * 4;
 
+// the bf16 tables from constant memory to the LDS at `lds` (the kernel's LDS 0): R, then (C,S)
+__device__ __forceinline__ void tab_bf16_fill(uint8_t* lds, int tid, int nthreads) {
+  float2* tabCS = reinterpret_cast<float2*>(lds + kLdsCsOff);
+  for (int i = tid; i < 256; i += nthreads) {
+    reinterpret_cast<float*>(lds)[i] = c_tab_bf16[i];
+    tabCS[i] = make_float2(c_tab_bf16[256 + i], c_tab_bf16[512 + i]);
+  }
+}
+
+// Thread q < 312 of a fast-segment workgroup owns Box-Muller pair q of every block: 16-block
+// q/8, slot q%8, i.e. block words j1 = 16*(q/8) + q%8 and j1 + 8 (DistributionTemplates.h:141-146),
+// which lie in one 16-block and so in one segment; pair_off is the LDS byte of that word pair in
+// window 0.  (Two functions returning values: as one function with two reference results the
+// compiler orders fks_apply_kernel's address arithmetic differently.)
+__device__ __forceinline__ int pair_word(int tid) { return 16 * (tid >> 3) + (tid & 7); }
+__device__ __forceinline__ int pair_off(int j1) { return kLdsTabBytes + 4 * wperm(j1); }
+
 // ------------------------------------------------------------------ fp32 Box-Muller
 // normal_fill_16_AVX2 (DistributionTemplates.h:88-106) with log256_ps / sincos256_ps
 // (avx_mathfun.h:90-160, 426-520) restated lane by lane; the fmaf()s are the

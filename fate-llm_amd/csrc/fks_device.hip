@@ -19,9 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-#include <atomic>
 #include <type_traits>
-#include <mutex>
 
 #include "fks_internal.h"
 #include "fks_bitslice.h"
@@ -66,11 +64,13 @@ constexpr int kBsFence = 8;      // slice kernel: compiler fence after every 8 s
 // The device code, one translation unit (c_tab_bf16 and ensure_tables() are shared by four
 // kernel families; no -fgpu-rdc): the shared layers, then one file per kernel family -- a
 // kernel file includes layers only, never another kernel file.  This file keeps the
-// tunables above, the once-per-device host setup and the launchers.
+// tunables above and the launchers; the once-per-device host setup is fks_dev_host.h.
 #include "fks_dev_lds.h"
 #include "fks_dev_update.h"
 #include "fks_dev_mt.h"
 #include "fks_dev_zgen.h"
+#include "fks_dev_irr.h"
+#include "fks_dev_host.h"
 #include "fks_kern_jump.h"
 #include "fks_kern_apply.h"
 #include "fks_kern_slice.h"
@@ -95,60 +95,6 @@ int device_cu_count() {
   if (hipGetDevice(&dev) != hipSuccess) return 256;
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
   return n;
-}
-
-// Once-per-DEVICE host setup: __constant__ memory and function attributes belong to
-// the device a call runs on, and one process may drive several GPUs (the plan cache
-// keys on the device id), so every such flag is a bitmask over device ids.
-class PerDevice {
- public:
-  template <class F>
-  int run(F&& f) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -FKS_EINVAL;
-    const uint64_t bit = 1ull << dev;
-    if (done_.load(std::memory_order_acquire) & bit) return 0;
-    std::lock_guard<std::mutex> lk(mu_);
-    if (done_.load(std::memory_order_relaxed) & bit) return 0;
-    const int e = f();
-    if (e == 0) done_.fetch_or(bit, std::memory_order_release);
-    return e;
-  }
-
- private:
-  std::mutex mu_;
-  std::atomic<uint64_t> done_{0};
-};
-
-static int ensure_tables() {
-  static PerDevice once;
-  return once.run([] {
-    const Tables& t = tables();
-    static float buf[3 * 2048];  // used under the PerDevice mutex only
-    for (int i = 0; i < 256; i++) {
-      buf[i] = t.r_bf16[i];
-      buf[256 + i] = t.c_bf16[i];
-      buf[512 + i] = t.s_bf16[i];
-    }
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_tab_bf16), buf, sizeof(float) * 768, 0, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return (int)e;
-    for (int i = 0; i < 2048; i++) {
-      buf[i] = t.r_f16[i];
-      buf[2048 + i] = t.c_f16[i];
-      buf[4096 + i] = t.s_f16[i];
-    }
-    e = hipMemcpyToSymbol(HIP_SYMBOL(c_tab_f16), buf, sizeof(buf), 0, hipMemcpyHostToDevice);
-    return (int)e;
-  });
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize for kernel `fn`, once per device
-template <class K>
-static int ensure_lds_attr(PerDevice& once, K* fn, int bytes) {
-  return once.run([&] {
-    return (int)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    bytes);
-  });
 }
 
 // A runtime value to a template argument: f(std::integral_constant<int, V>{}) for the V of
@@ -201,7 +147,7 @@ template <int DT, int MODE>
 static int launch_apply_t(const ApplyArgs& a, void* stream) {
   if (a.nseeds == kMaxSeedsPerPass) return launch_apply_f<DT, MODE, true>(a, stream);
   if constexpr (DT == FKS_BF16) {
-    // one-seed bf16 passes with a z-index buffer (fks_capi.cpp ZCache): store / replay
+    // one-seed bf16 passes with a z-index buffer (fks_cache.cpp ZCache): store / replay
     if (a.zmode == 1 && a.nseeds == 1 && MODE == kModePerturb) return launch_small2<DT, MODE, 1>(a, stream);
     if (a.zmode == 2 && a.nseeds == 1 &&
         (MODE == kModePerturb || MODE == kModePerturbUpdate || MODE == kModeUpdate || MODE == kModeUpdateWd ||

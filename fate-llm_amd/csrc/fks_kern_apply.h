@@ -72,11 +72,7 @@ __global__ __launch_bounds__(DB ? kDbThreads : kApplyThreads,
   const int64_t b0 = a.chunk_block[c], b1 = a.chunk_block[c + 1];
 
   if constexpr (DT == FKS_BF16) {
-    float2* tabCS = reinterpret_cast<float2*>(lds + kLdsCsOff);
-    for (int i = tid; i < 256; i += kApplyThreads) {
-      reinterpret_cast<float*>(lds)[i] = c_tab_bf16[i];
-      tabCS[i] = make_float2(c_tab_bf16[256 + i], c_tab_bf16[512 + i]);
-    }
+    tab_bf16_fill(lds, tid, kApplyThreads);
   } else if constexpr (DT == kDtF32Libm) {
     logf_tab_fill(0u, tid, DB ? kDbThreads : kApplyThreads);
   }
@@ -108,11 +104,10 @@ __global__ __launch_bounds__(DB ? kDbThreads : kApplyThreads,
     __syncthreads();
   }
 
-  // Thread q < 312 owns Box-Muller pair q of every block: 16-block q/8, slot q%8,
-  // i.e. block words j1 = 16*(q/8) + q%8 and j1 + 8 (DistributionTemplates.h:141-146).
+  // Thread q < 312 owns Box-Muller pair q of every block: block words j1 and j1 + 8 (pair_word)
   const bool lane_on = tid < kMtN / 2;
-  const int j1 = 16 * (tid >> 3) + (tid & 7);
-  const int st_off = kLdsTabBytes + 4 * wperm(j1);  // the (j1, j1 + 8) word pair
+  const int j1 = pair_word(tid);
+  const int st_off = pair_off(j1);  // the (j1, j1 + 8) word pair
 
   // The lane's current segment, cached in registers; positions only grow.
   int cur;
@@ -279,10 +274,7 @@ __global__ __launch_bounds__(kSm2Threads, kSm2MinWaves) void fks_small2_kernel(A
   const int nblk = (int)(a.chunk_block[c + 1] - b0);  // host: a chunk is far below 2^31 blocks
 
   if constexpr (DT == FKS_BF16) {
-    for (int i = tid; i < 256; i += (int)blockDim.x) {
-      reinterpret_cast<float*>(lds)[i] = c_tab_bf16[i];
-      reinterpret_cast<float2*>(lds + kLdsCsOff)[i] = make_float2(c_tab_bf16[256 + i], c_tab_bf16[512 + i]);
-    }
+    tab_bf16_fill(lds, tid, (int)blockDim.x);
   } else if constexpr (DT == kDtF32Libm) {
     logf_tab_fill(0u, tid, kSm2Threads);
   }

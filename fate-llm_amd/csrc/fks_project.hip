@@ -212,12 +212,6 @@ struct ProjFetchTable {
   }
 };
 
-__device__ __forceinline__ double proj_wave_sum(double x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-  return x;
-}
-
 // Every seed of the pass over the wave's groups whose tensors draw dtype DT (`mine`: this
 // lane has such a group): the whole wave runs this, lanes that are not `mine` enter +0.
 // The z of a seed are drawn once; each of the NV vectors runs its own chain, q then i.
@@ -275,7 +269,7 @@ __device__ __forceinline__ void proj_seeds(const Args& a, uint64_t ctr, uint32_t
     }
 #pragma unroll
     for (int m = 0; m < NV; m++) {
-      const double total = proj_wave_sum(mine ? part[m] : 0.0);
+      const double total = wave_sum(mine ? part[m] : 0.0);
       acc[m] += lane == k ? total : 0.0;
     }
   }
@@ -380,7 +374,7 @@ __global__ __launch_bounds__(64) void fks_project_reduce_kernel(const double* pa
   const int k = (int)blockIdx.x, m = (int)blockIdx.y, nv = (int)gridDim.y;
   double s = 0.0;
   for (int b = (int)threadIdx.x; b < nblocks; b += 64) s += partial[((size_t)b * nv + m) * kPhxSeeds + k];
-  s = proj_wave_sum(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) out[(int64_t)m * out_stride + k] = s;
 }
 

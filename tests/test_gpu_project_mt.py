@@ -25,10 +25,16 @@ Tensor list, per dtype, the smallest that reaches every branch of the two kernel
   65,536     an irregular run whose 16-blocks straddle MT block boundaries
   0          empty
   48         a short run at a non-zero phase
-(for f16 every run is irregular); k = 1 (a partial pass), 19 (one full pass), 20 (full + partial)."""
+(for f16 every run is irregular); k = 1 (a partial pass), 19 (one full pass), 20 (full + partial).
+
+The bounds above leave the summation order free, but fks.h promises one fixed order, so the bits
+are pinned too: tests/golden/project_mt_parent.json holds what the library of a recorded commit
+returned for this list (tests/golden/make_project_mt_parent.py writes it with record_bits below)."""
 import ctypes
 import functools
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -168,6 +174,43 @@ def _one_hot(specs, seeds, total, probes, zp, live, dev, v=float(np.float32(-3.1
         if not np.array_equal(got, want):  # bit for bit but for the sign of a zero
             bad.append((e, int((got != want).sum())))
     return bad
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "project_mt_parent.json")
+
+
+def _cu_count():
+    return int(torch.cuda.get_device_properties(_dev()).multi_processor_count)
+
+
+def record_bits():
+    """The int64 bit patterns of codec.project_mt over SIZES, the dense vector and the 20 SEEDS
+    (one full and one partial pass), per dtype, and for fp32 under the libm flavour."""
+    from fate_llm.algo.fedkseed import codec
+    dense = _case("float32")["vec"].to(_dev())  # the vector does not depend on the dtype
+    bits = {d: _i64(codec.project_mt(_specs(d), SEEDS, dense)).tolist() for d in DTYPES}
+    codec.set_cpu_fp32_flavour("libm")
+    try:
+        bits["float32_libm"] = _i64(codec.project_mt(_specs("float32"), SEEDS, dense)).tolist()
+    finally:
+        codec.set_cpu_fp32_flavour(None)
+    return bits
+
+
+def test_bits_equal_parent_recording():
+    """The summation order is part of the interface (fks.h: one fixed order): every result equals,
+    bit for bit, what the recorded commit's library returned.  The order is a function of the
+    plan's chunk count, which follows the device's CU count: on another device nothing is pinned."""
+    with open(GOLDEN) as f:
+        gold = json.load(f)
+    if _cu_count() != gold["cu_count"]:
+        pytest.skip(f"recorded on a device of {gold['cu_count']} CUs, this one has {_cu_count()}")
+    got = record_bits()
+    assert sorted(got) == sorted(gold["bits"])
+    for name, want in gold["bits"].items():
+        assert len(want) == len(SEEDS)
+        differ = [i for i, (a, b) in enumerate(zip(got[name], want)) if a != b]
+        assert not differ, f"{name}: seeds {differ} differ from commit {gold['commit']} (build {gold['build_id']})"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

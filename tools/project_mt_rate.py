@@ -1,17 +1,18 @@
 """The MT19937-stream projection's cost beside its adjoint (one MI355X).
 
-Per layout -- the 291 bf16 tensors of Llama-2-7B, and one fp32 tensor of 2^28 elements -- and in
-one process, one 19-seed pass each of
+Per layout -- the 291 bf16 tensors of Llama-2-7B, one fp32 tensor of 2^28 elements, and one f16
+tensor of 2^26 elements -- and in one process, one 19-seed pass each of
   codec.project_mt                      (fks_project_mt: jumps, fks_project_mt_kernel, reduce)
   codec.delta_accumulate on torch_cpu   (fks_delta_accumulate: jumps, fks_apply_kernel kModeDelta)
 the like-for-like 19-seed kernels on the same plan: the projection reads the 4-byte vector
-element and writes nothing, the delta reads and writes 4 bytes.  For scale, one 32-seed
+element and writes nothing, the delta reads and writes 4 bytes.  Every f16 run is irregular, so
+the third layout times fks_project_mt_irr_kernel and fks_irregular_kernel<kModeDelta>.  For scale, one 32-seed
 codec.project launch on the torch_rocm stream over the same layout, as ms per seed.
 HIP events around each call on the current stream, warm-ups first, then the median of --calls
 timed calls with their minimum and maximum (the run-to-run spread).  No threshold: the figures
 go to DESIGN.md.
 
-Prints one JSON line per layout.  python tools/project_mt_rate.py [--calls 20] [--warmup 3]"""
+Prints one JSON line per layout.  python tools/project_mt_rate.py [--calls 20] [--warmup 3] [--layout all|7b|f32|f16]"""
 import argparse
 import json
 import os
@@ -79,14 +80,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--layout", choices=("all", "7b", "f32", "f16"), default="all")
     args = ap.parse_args()
     if args.calls < 10:
         ap.error("--calls must be at least 10 (the figure is a median)")
     dev = torch.device("cuda", 0)
-    numels = [int(torch.Size(s).numel()) for s in bench.llama7b_shapes()]
-    _layout("Llama-2-7B layout, bf16", numels, torch.bfloat16, dev, args.calls, args.warmup)
-    torch.cuda.empty_cache()
-    _layout("one fp32 tensor of 2^28 elements", [1 << 28], torch.float32, dev, args.calls, args.warmup)
+    if args.layout in ("all", "7b"):
+        numels = [int(torch.Size(s).numel()) for s in bench.llama7b_shapes()]
+        _layout("Llama-2-7B layout, bf16", numels, torch.bfloat16, dev, args.calls, args.warmup)
+        torch.cuda.empty_cache()
+    if args.layout in ("all", "f32"):
+        _layout("one fp32 tensor of 2^28 elements", [1 << 28], torch.float32, dev, args.calls, args.warmup)
+        torch.cuda.empty_cache()
+    if args.layout in ("all", "f16"):
+        _layout("one f16 tensor of 2^26 elements (irregular kernels)", [1 << 26], torch.float16, dev, args.calls,
+                args.warmup)
 
 
 if __name__ == "__main__":
