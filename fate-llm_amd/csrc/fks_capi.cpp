@@ -219,6 +219,50 @@ int fks_project_mt(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32
   });
 }
 
+// ... several vectors, each read where it lies
+static void project_mt_multi_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_project_mt_multi: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_project_multi is the call for that stream");
+}
+
+int fks_project_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    project_mt_multi_check_stream(t, nt);
+    *bytes = project_mt_multi_ws(t, nt, k, nvec, 0, 1, device_cu_count()).total;
+  });
+}
+
+int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
+                         int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
+                         size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    if (nvec < 0) throw Error(-FKS_EINVAL, "negative vector count");
+    check_shard(shard, nshards);
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (nvec > 0 && nt > 0 && !vecs) throw Error(-FKS_EINVAL, "null vector list");
+    for (int m = 0; m < nvec; m++)
+      for (int i = 0; i < nt; i++) {
+        if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
+        const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+        if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
+          throw Error(-FKS_EINVAL, "vector " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad vector dtype " +
+                                       std::to_string(v.dtype));
+        if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
+          throw Error(-FKS_EINVAL, "vector " + std::to_string(m) + ", tensor " + std::to_string(i) +
+                                       ": null or misaligned vector pointer");
+      }
+    if (k > 0 && nvec > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned projection output");
+    project_mt_multi_check_stream(t, nt);
+    if (k == 0 || nvec == 0) return;
+    project_mt_multi(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
 int fks_directional_step(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* values, int32_t k,
                          int32_t value_kind, void* workspace, size_t ws_bytes, void* stream) {
   return guarded([&] { run(t, nt, seeds, values, k, value_kind, kModeUpdate, workspace, ws_bytes, stream); });

@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "fks_internal.h"
+#include "fks_project_mt.h"
 
 namespace fks {
 
@@ -106,8 +107,18 @@ struct ProjMtWs {
   size_t partial_off = 0, total = 0;  // where the partial rows start; bytes in all
   int rows = 0;                       // partial rows of one pass, at most
   bool work = false;                  // the shard holds an element of a non-frozen tensor
+  int entries = 0;                    // descriptors of the shard's plan: fast segments + runs + single elements
 };
 ProjMtWs project_mt_ws(const fks_tensor* t, int nt, int k, int shard, int nshards, int cus);
+// fks_project_mt_multi's: [vector table: nvec x entries pieces | fks_project_mt's layout, its
+// partial rows widened to the vectors of one pass]
+struct ProjMtMultiWs {
+  ProjMtWs one;            // the one-vector layout behind the table (offsets from inner_off)
+  size_t inner_off = 0;    // bytes of the table, 256-aligned
+  size_t total = 0;
+  int pass_vec = 0;        // vectors per pass: min(nvec, kProjMtMaxVec), at least 1
+};
+ProjMtMultiWs project_mt_multi_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -289,5 +300,8 @@ void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fl
 // fks_project_mt: the same projection on the CPU generator's stream (the kModeDelta plan of vec)
 void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
                 double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_project_mt_multi: nvec vectors read in place (vecs[nvec][nt]) over the geometry-only plan
+void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
+                      int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 
 }  // namespace fks

@@ -295,9 +295,24 @@ ProjMtWs project_mt_ws(const fks_tensor* t, int nt, int k, int shard, int nshard
   for (auto& x : irregular_owner_intervals(L)) covered += x.second - x.first;
   const int irr = covered ? plan_nchunks(covered, false, cus) : 0;
   w.work = ndt > 0 || irr > 0;
+  w.entries = nsegs_total(L) + (int)L.runs.size() + (int)L.tiny.size();
   w.rows = ndt * reg + irr;
   w.partial_off = align_up(ws_bytes_for(std::max(reg, irr), std::max(1, std::min(k, kMaxSeedsPerPass))), 256);
   w.total = w.partial_off + sizeof(double) * (size_t)kPhxSeeds * (size_t)std::max(w.rows, 1);
+  return w;
+}
+
+// fks_project_mt_multi's workspace: the per-call table of vector pieces in front -- one entry per
+// vector and descriptor of the shard's plan (clipping drops or shortens descriptors, it never
+// splits one: the whole list's count bounds every shard's) --, then fks_project_mt's layout with
+// the partial rows of the vectors of one pass, [row][vector][kPhxSeeds].
+ProjMtMultiWs project_mt_multi_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus) {
+  ProjMtMultiWs w;
+  w.one = project_mt_ws(t, nt, k, shard, nshards, cus);
+  w.pass_vec = std::max(1, std::min(nvec, kProjMtMaxVec));
+  w.inner_off = align_up(sizeof(ProjMtVecEntry) * (size_t)std::max(nvec, 0) * (size_t)w.one.entries, 256);
+  w.total = w.inner_off + w.one.partial_off +
+            sizeof(double) * (size_t)kPhxSeeds * (size_t)w.pass_vec * (size_t)std::max(w.one.rows, 1);
   return w;
 }
 

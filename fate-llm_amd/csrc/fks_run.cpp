@@ -600,4 +600,128 @@ void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const
   }
 }
 
+// ---- ... of several vectors, each read where it lies ----
+// project_mt over the geometry-only plan (the kModeDelta plan of kProjMtGeoBase: one cache entry
+// per tensor list and shard, whatever the vectors' addresses) and a per-call table at the front of
+// the workspace, uploaded in stream order: per vector, its piece under every fast segment (the
+// dtypes' segments behind each other, as in the plan), run and single element.  The vectors go in
+// batches of kProjMtMaxVec over the same seeds; a batch of nv vectors takes its seeds in passes of
+// proj_mt_pass_seeds(nv), each the launches of a project_mt pass with rows of nv sums per seed.
+void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
+                      int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ProjMtMultiWs W = project_mt_multi_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.one.work) {  // nothing in this shard: every projection is +0
+    const size_t bytes = sizeof(double) * (size_t)k * (size_t)nvec;
+    check_hip(hipMemsetAsync(dev_out, 0, bytes, (hipStream_t)stream), "hipMemsetAsync");
+    return;
+  }
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < W.total)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(W.total) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  // the table on the host, from the layout the plan is built from
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  clip_segments(L, shard_blocks(L.stream_len, shard, nshards));
+  const size_t nsegs = L.segs[0].size() + L.segs[1].size() + L.segs[2].size();
+  const size_t E = nsegs + L.runs.size() + L.tiny.size();
+  if (E != (size_t)W.one.entries) throw Error(-FKS_EINVAL, "the layout does not match the call's workspace layout");
+  std::vector<int64_t> start((size_t)nt, 0);  // the tensors' first elements in the concatenation
+  for (int i = 1; i < nt; i++) start[i] = start[i - 1] + t[i - 1].numel;
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  host.assign((size_t)nvec * E, ProjMtVecEntry{});
+  for (int m = 0; m < nvec; m++) {
+    ProjMtVecEntry* x = host.data() + (size_t)m * E;
+    // a descriptor of tensor i whose element 0 is element (ptr - base) / 4 of the concatenation
+    auto put = [&](int i, uint64_t ptr) {
+      const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+      const int64_t e = (int64_t)((ptr - kProjMtGeoBase) / 4) - start[i];
+      x->ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)e * elem_size(v.dtype);
+      x->dtype = v.dtype;
+      x++;
+    };
+    for (int d = 0; d < 3; d++)
+      for (size_t j = 0; j < L.segs[d].size(); j++) put(L.seg_tensor[d][j], L.segs[d][j].ptr);
+    for (size_t j = 0; j < L.runs.size(); j++) put(L.run_tensor[j], L.runs[j].ptr);
+    for (size_t j = 0; j < L.tiny.size(); j++) put(L.tiny_tensor[j], L.tiny[j].ptr);
+  }
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  int rows = C->have_irr ? C->Z.irr_chunks : 0;
+  for (int d = 0; d < 3; d++) rows += C->nsegs[d] ? C->Z.reg_chunks : 0;
+  bool same = (size_t)C->Z.nsegs == nsegs && (size_t)C->Z.nruns == L.runs.size() && (size_t)C->Z.ntiny == L.tiny.size();
+  for (int d = 0; d < 3; d++) same = same && (size_t)C->nsegs[d] == L.segs[d].size();
+  if (!same || rows < 1 || rows > W.one.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.one.partial_off)
+    throw Error(-FKS_EINVAL, "the plan does not match the call's workspace layout");
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  uint8_t* ws = static_cast<uint8_t*>(workspace) + W.inner_off;
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  double* const partial = reinterpret_cast<double*>(ws + W.one.partial_off);
+  for (int m0 = 0; m0 < nvec; m0 += kProjMtMaxVec) {  // batches of vectors over the same seeds
+    const int nv = std::min(kProjMtMaxVec, nvec - m0);
+    const int per_pass = proj_mt_pass_seeds(nv);
+    const ProjMtVecEntry* tab = table + (size_t)m0 * E;
+    for (int s0 = 0; s0 < k; s0 += per_pass) {
+      const int nb = std::min(per_pass, k - s0);
+      double* row = partial;
+      if (C->have_reg) {
+        JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_polys, C->H.off_cb, states, C->Z.reg_chunks);
+        ja.chunks_per_wg = jump_chunks_per_wg(nb, C->Z.reg_chunks, dc.cus);
+        check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+        size_t seg0 = 0;  // the dtype's first segment in the table row
+        for (int d = 0; d < 3; d++) {
+          const size_t first = seg0;
+          seg0 += (size_t)C->nsegs[d];
+          if (!C->nsegs[d]) continue;
+          ProjMtMultiArgs pa{};
+          pa.states = states;
+          pa.segs = reinterpret_cast<const DevSeg*>(hdr + C->seg_off[d]);
+          pa.chunk_block = ja.chunk_block;
+          pa.sink = reinterpret_cast<const uint64_t*>(ws);
+          pa.partial = row;
+          pa.pv = tab + first;
+          pa.stride = (int64_t)E;
+          pa.nsegs = C->nsegs[d];
+          pa.nchunks = C->Z.reg_chunks;
+          pa.nseeds = nb;
+          pa.nvec = nv;
+          const int dd = (d == FKS_F32 && libm) ? kDtF32Libm : d;
+          check_launch(timed(0, stream, [&] { return launch_project_mt_multi(dd, pa, stream); }),
+                       "fks_project_mt_multi_kernel", "bad arguments");
+          row += (size_t)kPhxSeeds * (size_t)nv * (size_t)C->Z.reg_chunks;
+        }
+      }
+      if (C->have_irr) {
+        JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_ipolys, C->H.off_ilo, states, C->Z.irr_chunks);
+        ja.chunks_per_wg = std::max(1, std::min(32, C->Z.irr_chunks));
+        check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+        ProjMtIrrMultiArgs ia{};
+        ia.states = states;
+        ia.runs = reinterpret_cast<const DevRun*>(hdr + C->H.off_runs);
+        ia.tiny = reinterpret_cast<const DevTiny*>(hdr + C->H.off_tiny);
+        ia.chunk_lo = ja.chunk_block;
+        ia.chunk_hi = reinterpret_cast<const int64_t*>(hdr + C->H.off_ihi);
+        ia.partial = row;
+        ia.rv = tab + nsegs;
+        ia.tv = tab + nsegs + L.runs.size();
+        ia.stride = (int64_t)E;
+        ia.nruns = C->Z.nruns;
+        ia.ntiny = C->Z.ntiny;
+        ia.nchunks = C->Z.irr_chunks;
+        ia.nseeds = nb;
+        ia.libm = libm ? 1 : 0;
+        ia.nvec = nv;
+        check_launch(timed(0, stream, [&] { return launch_project_mt_irr_multi(ia, stream); }),
+                     "fks_project_mt_irr_multi_kernel", "bad arguments");
+      }
+      check_launch(launch_project_reduce(partial, rows, nb, nv, dev_out + (size_t)m0 * (size_t)k + s0, k, stream),
+                   "fks_project_reduce_kernel", "bad arguments");
+    }
+  }
+}
+
 }  // namespace fks

@@ -727,14 +727,45 @@ def project_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, str
     queued on the current stream without synchronisation once the spec list has a cached plan
     (the plan does not depend on where the vectors live); the vectors are kept alive until the
     call is queued.  Draws nothing from torch's generators.  torch_rocm stream only: a call
-    that resolves to torch_cpu raises NotImplementedError."""
+    that resolves to torch_cpu raises NotImplementedError (``project_mt_multi`` is that stream's
+    call; ``zo_utils.seed_projections_in_place`` picks between the two)."""
     specs = list(specs)
     vectors = [list(v) for v in vectors]
     device = specs[0].tensor.device if specs else torch.device("cpu")
     mode = resolve_stream_mode(device, stream_mode)
     if mode != "torch_rocm":
         raise NotImplementedError(f"FedKSeed codec: project_multi() is built for the torch_rocm stream only; this call "
-                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws)")
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), whose in-place "
+                                  f"call is project_mt_multi()")
+    return _project_in_place(specs, seeds, vectors, mode, shard, nshards)
+
+
+# vectors that share one pass of the generator in project_mt_multi (csrc/fks_project_mt.h
+# FKS_PMT_MAX_VEC; more run in batches, with the same bits)
+PROJECT_MT_PASS_VECTORS = 2
+
+
+def project_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, shard: int = 0,
+                     nshards: int = 1) -> torch.Tensor:
+    """``project_multi`` on the torch_cpu stream (include/fks.h fks_project_mt_multi): out[m, s] =
+    <vectors[m], z_s> over the non-frozen specs' elements that element shard ``shard`` of
+    ``nshards`` owns (``project_mt``'s shards), z_s the CPU generator's MT19937 draw for seeds[s]
+    in each spec's dtype -- fp32 in the process's flavour (``cpu_fp32_flavour``), as
+    ``project_mt``.  ``vectors``, the argument checks, the staging and the keep-alive are
+    ``project_multi``'s: M sequences with one tensor (or None, for a frozen spec only) per spec; a
+    contiguous float32 / bfloat16 / float16 tensor on the specs' device is read in place, in its
+    own dtype; any other float tensor gets a contiguous f32 copy of that tensor only.  It takes no
+    ``stream_mode`` (the stream is always torch_cpu) and has no CPU path.  The twist and the
+    Box-Muller of a seed run once for two vectors (more run in batches); row m equals the one-vector call on
+    vectors[m] bit for bit, and a one-vector call on f32 views of one buffer equals
+    ``project_mt`` on that buffer bit for bit.  Returns float64[M, K] on the specs' device, queued
+    on the current stream; the plan depends on the spec list alone, not on where the vectors
+    live.  Draws nothing from torch's generators and leaves them alone."""
+    return _project_in_place(list(specs), seeds, [list(v) for v in vectors], "torch_cpu", shard, nshards)
+
+
+def _project_in_place(specs, seeds, vectors, mode, shard, nshards) -> torch.Tensor:
+    """project_multi (torch_rocm) and project_mt_multi (torch_cpu) behind their stream checks."""
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     M, n = len(vectors), len(specs)
@@ -771,13 +802,14 @@ def project_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, str
     if not out.numel():
         return out
     L = N.load()
+    size_fn, fn = ((L.fks_project_multi_workspace_size, L.fks_project_multi) if mode == "torch_rocm" else
+                   (L.fks_project_mt_multi_workspace_size, L.fks_project_mt_multi))
     with torch.cuda.device(b.device):
         nbytes = ctypes.c_size_t(0)
-        N.check(L.fks_project_multi_workspace_size(ctypes.addressof(b.arr), b.n, len(s), M, ctypes.byref(nbytes)))
+        N.check(size_fn(ctypes.addressof(b.arr), b.n, len(s), M, ctypes.byref(nbytes)))
         ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
-        N.check(L.fks_project_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), ctypes.addressof(varr), M,
-                                    int(shard), int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
-                                    _stream_handle(b.device)))
+        N.check(fn(ctypes.addressof(b.arr), b.n, s.ctypes.data, len(s), ctypes.addressof(varr), M, int(shard),
+                   int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
     del keep  # queued: the copies and ws go back to torch's allocator in stream order
     return out
 

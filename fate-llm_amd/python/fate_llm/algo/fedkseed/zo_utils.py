@@ -289,7 +289,8 @@ def seed_projections_multi(param_groups: List[dict], seeds: Sequence[int], vecto
     (codec.project_multi).  ``vector_lists``: M lists with one tensor per parameter (None for
     a parameter that does not require grad); default: one list, every parameter's ``.grad``,
     and a [1, K] result.  Row m equals the one-list call on list m bit for bit, and equals
-    ``seed_projections`` of the same vectors bit for bit."""
+    ``seed_projections`` of the same vectors bit for bit.  torch_rocm stream only: a call that
+    resolves to torch_cpu raises; ``seed_projections_in_place`` takes either stream."""
     specs, vector_lists, _ = _projection_specs(param_groups, vector_lists)
     if not specs:
         return torch.zeros((len(vector_lists), len(seeds)), dtype=torch.float64)
@@ -300,11 +301,48 @@ def fit_seed_scalars_multi(param_groups: List[dict], seeds: Sequence[int], delta
                            stream_mode=None) -> torch.Tensor:
     """``fit_seed_scalars`` of M dense deltas in one call: ``seed_projections_multi / N``,
     float64[M, K] -- an arbiter turning the deltas of several first-order or FedAvg parties
-    into (seed, scalar) form pays for one pass of the generator per four parties."""
+    into (seed, scalar) form pays for one pass of the generator per four parties.  torch_rocm
+    stream only; ``fit_seed_scalars_in_place`` takes either stream."""
     specs, vector_lists, n_live = _projection_specs(param_groups, delta_vector_lists)
     if not specs or n_live == 0:
         raise ValueError("fit_seed_scalars_multi: no parameter requires grad")
     return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode) / float(n_live)
+
+
+def _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode):
+    """codec.project_multi on the torch_rocm stream, codec.project_mt_multi on torch_cpu: the
+    stream the call resolves to on the parameters' device."""
+    if codec.resolve_stream_mode(specs[0].tensor.device, stream_mode) == "torch_cpu":
+        return codec.project_mt_multi(specs, seeds, vector_lists)
+    return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode)
+
+
+def seed_projections_in_place(param_groups: List[dict], seeds: Sequence[int], vector_lists=None,
+                              stream_mode=None) -> torch.Tensor:
+    """``seed_projections_multi`` on either stream, float64[M, K]: a call that resolves to
+    torch_rocm takes codec.project_multi, one that resolves to torch_cpu codec.project_mt_multi.
+    Every vector is read where it lies, in its own dtype -- no f32 buffer of the model's size, no
+    conversion pass, no plan keyed on a buffer's address -- and up to four lists (torch_rocm) or
+    two (torch_cpu) share each pass of the generator.  ``vector_lists`` and the default (one list, every parameter's ``.grad``,
+    a [1, K] result; a missing grad on a parameter that requires grad is an error) are
+    ``seed_projections_multi``'s.  Row m equals the one-list call on list m bit for bit, and
+    equals ``seed_projections`` of the same vectors on the same stream bit for bit.  torch's
+    generators are left alone."""
+    specs, vector_lists, _ = _projection_specs(param_groups, vector_lists)
+    if not specs:
+        return torch.zeros((len(vector_lists), len(seeds)), dtype=torch.float64)
+    return _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
+
+
+def fit_seed_scalars_in_place(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                              stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars_multi`` on either stream: ``seed_projections_in_place / N``,
+    float64[M, K], through codec.project_multi (torch_rocm) or codec.project_mt_multi
+    (torch_cpu)."""
+    specs, vector_lists, n_live = _projection_specs(param_groups, delta_vector_lists)
+    if not specs or n_live == 0:
+        raise ValueError("fit_seed_scalars_in_place: no parameter requires grad")
+    return _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode) / float(n_live)
 
 
 def build_seed_candidates(k, low=0, high=2**32):

@@ -370,6 +370,43 @@ int fks_project_mt_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, si
 int fks_project_mt(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const float* vec, int32_t shard,
                    int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- ... of several vectors, each read where it lies ----
+ * fks_project_mt_multi: fks_project_multi's contract on fks_project_mt's stream.
+ * dev_out[m * k + s] = sum over the non-frozen tensors i and the elements e that element shard
+ * `shard` of `nshards` owns of (double)f32(vecs[m * nt + i][e]) * (double)z_s(i, e), m < nvec,
+ * s < k.  vecs is a HOST array of nvec x nt fks_vec entries; entry m * nt + i is a DEVICE pointer
+ * to vector m's t[i].numel contiguous elements of its own dtype (FKS_F32, FKS_BF16 or FKS_F16,
+ * widened to f32 exactly), aligned to its element size only; entries of frozen and empty tensors
+ * are ignored and may be NULL.  z_s is what fks_normal writes for seeds[s] on the CPU generator's
+ * stream (the FKS_LIBM flavour where the list carries it); frozen tensors advance the stream and
+ * contribute nothing; the shards are fks_project_mt's whole MT blocks.  No model-size staging
+ * buffer exists anywhere.  Two vectors share one pass of the generator -- the twist and the
+ * Box-Muller of a seed run once for both --; a larger nvec runs in batches of 2 over the same
+ * seeds.  A pass of one vector carries 19 seeds, one of two vectors 10: the order of one seed's
+ * additions does not depend on the seeds that share its pass.
+ * Every product is exact in f64 and every vector's additions run in fks_project_mt's order (a
+ * lane's fma chain over its elements of a plan chunk, the 64-lane butterfly, the waves in wave
+ * order, the chunks' rows of the pass's launches in row order; no floating-point atomic):
+ *   - row m of a call with nvec vectors equals the nvec == 1 call on vector m, bit for bit;
+ *   - a one-vector call whose entries are f32 and lie end to end in one 8-byte aligned buffer
+ *     equals fks_project_mt on that buffer, bit for bit;
+ * for every k, shard and dtype: a result depends neither on how the caller batches its vectors,
+ * nor on a vector's dtype beyond its values, nor on its alignment.  dev_out (nvec * k doubles,
+ * device memory, 8-byte aligned) is OVERWRITTEN in stream order.  The tensors' data pointers are
+ * not read and the vectors' addresses key no cached plan (one geometry-only plan per tensor list
+ * and shard); the per-call table of vector pieces travels at the front of the workspace, uploaded
+ * in stream order.  k == 0, nvec == 0, nt == 0 and all-empty lists succeed; a shard with no
+ * element zeroes its nvec * k outputs.  Workspace: fks_project_mt_multi_workspace_size (8-byte
+ * aligned; a function of the list, k, nvec and the device's CU count).  Errors, raised from the
+ * arguments alone before any allocation or launch: those of fks_project_mt, nvec < 0, a NULL vecs
+ * with nvec > 0 and nt > 0, a vector dtype outside the three, a NULL or misaligned vector pointer
+ * for a non-frozen, non-empty tensor: -FKS_EINVAL; a list that carries FKS_STREAM_ROCM:
+ * -FKS_ENOTSUP (fks_project_multi is the call for that stream).                              */
+int fks_project_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
+int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
+                         int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
+                         size_t ws_bytes, void* stream);
+
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
