@@ -188,6 +188,67 @@ int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, in
   });
 }
 
+// ---- seed-basis expansion (torch_rocm stream) ----
+static void expand_check_stream(const fks_tensor* t, int nt) {
+  if (nt == 0 || rocm_stream(t, nt)) return;
+  throw Error(-FKS_ENOTSUP, std::string("fks_expand_multi: the torch_cpu stream (the CPU generator's MT19937 stream") +
+                                (libm_flavour(t, nt) ? ", FKS_LIBM flavour" : "") +
+                                ") is not supported; expansion is built for FKS_STREAM_ROCM (torch_rocm) only, "
+                                "fks_delta_accumulate sums either stream into an f32 buffer");
+}
+
+int fks_expand_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    expand_check_stream(t, nt);
+    *bytes = expand_ws_bytes(t, nt, k, nvec);
+  });
+}
+
+int fks_expand_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                     const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                     void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    if (nvec < 0) throw Error(-FKS_EINVAL, "negative output count");
+    check_shard(shard, nshards);
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (k > 0 && nvec > 0 && !coefs) throw Error(-FKS_EINVAL, "null coefficient array");
+    if (nvec > 0 && nt > 0 && !outs) throw Error(-FKS_EINVAL, "null output list");
+    for (int m = 0; m < nvec; m++)
+      for (int i = 0; i < nt; i++) {
+        if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
+        const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
+        if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
+          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad output dtype " +
+                                       std::to_string(v.dtype));
+        if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
+          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) +
+                                       ": null or misaligned output pointer");
+      }
+    expand_check_stream(t, nt);
+    if (nvec == 0 || nt == 0) return;
+    expand(t, nt, seeds, coefs, k, outs, betas, nvec, shard, nshards, workspace, ws_bytes, stream);
+  });
+}
+
+int fks_expand_launch_cuts(const fks_tensor* t, int32_t nt, int32_t k, int32_t shard, int32_t nshards, int64_t work,
+                           int64_t max_grid, int64_t* cuts, int32_t cap, int32_t* ncuts) {
+  return guarded([&] {
+    validate(t, nt);
+    check_shard(shard, nshards);
+    if (k < 0 || cap < 0 || !ncuts || (cap > 0 && !cuts)) throw Error(-FKS_EINVAL, "bad arguments");
+    expand_check_stream(t, nt);
+    const PhxGeo geo = phx_geometry(t, nt, nullptr, 0, max_grid > 0 ? max_grid : device_caps().max_grid);
+    const std::vector<int64_t> b = phx_expand_cuts(geo, phx_boundary(geo, shard, nshards),
+                                                   phx_boundary(geo, shard + 1, nshards), k,
+                                                   work > 0 ? work : expand_launch_work());
+    *ncuts = (int32_t)std::min<size_t>(b.size(), (size_t)INT32_MAX);
+    for (size_t i = 0; i < b.size() && i < (size_t)cap; i++) cuts[i] = b[i];
+  });
+}
+
 // ---- seed-basis projection (CPU generator's stream) ----
 static void project_mt_check_stream(const fks_tensor* t, int nt) {
   if (rocm_stream(t, nt))

@@ -11,6 +11,7 @@
 
 #include "fks_internal.h"
 #include "fks_project_mt.h"
+#include "fks_expand.h"
 
 namespace fks {
 
@@ -190,6 +191,9 @@ PhxGeo phx_geometry(const fks_tensor* t, int nt, const double* scales, uint64_t 
 int64_t phx_boundary(const PhxGeo& P, int shard, int nshards);  // shard's first work item
 int64_t phx_boundary_elem(const PhxGeo& P, int64_t b);
 void phx_census(const PhxGeo& P, int nt, int shard, int nshards, int64_t* word_range, int64_t* written);
+// fks_expand_multi's launch cuts of the items [lo, hi): row boundaries lo = b[0] < ... < b[n] = hi, each
+// launch at most `work` seed-elements (4 per item x max(k, 1)) or a single row
+std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, int k, int64_t work);
 
 // ================================================================== fks_cache.cpp
 // the current device and what the planning reads of it, read once per call
@@ -303,5 +307,10 @@ void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const
 // fks_project_mt_multi: nvec vectors read in place (vecs[nvec][nt]) over the geometry-only plan
 void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
                       int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_expand_multi: nvec outputs written in place (outs[nvec][nt]), coefs[nvec][k], betas[nvec] or null
+int64_t expand_launch_work();  // kExpLaunchWork, or FKS_EXPAND_WORK where it is set to a positive number
+size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec);
+void expand(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+            const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream);
 
 }  // namespace fks

@@ -129,6 +129,35 @@ int64_t phx_boundary_elem(const PhxGeo& P, int64_t b) {
   return P.elem0[k] + std::min<int64_t>(T.numel, 4 * ((b - T.item0) / T.stride) * (int64_t)T.stride);
 }
 
+// Launch cuts of fks_expand_multi, whose one launch would otherwise carry every seed of the call
+// over the whole shard: the items [lo, hi) (row boundaries, phx_boundary) as b[0] = lo < b[1] < ...
+// < b[n] = hi, every b a row boundary, a launch [b[i], b[i + 1]) holding at most `work`
+// seed-elements -- 4 elements per item (a row's ragged end counts whole) times max(k, 1) seeds --
+// or else exactly one row.  Greedy: each launch takes as many whole rows as fit.  Empty for lo >= hi.
+std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, int k, int64_t work) {
+  std::vector<int64_t> b;
+  if (lo >= hi || P.nt == 0) return b;
+  const int64_t per_item = 4 * (int64_t)std::max(k, 1);
+  const int64_t budget = std::max<int64_t>(1, work / per_item);  // items per launch
+  b.push_back(lo);
+  for (int64_t cur = lo; cur < hi;) {
+    int64_t next = hi;
+    if (hi - cur > budget) {
+      const PhxTensor& T = P.tab[phx_entry(P, cur + budget)];  // cur + budget < hi <= P.items: inside T
+      const int64_t S = T.stride;
+      next = T.item0 + (cur + budget - T.item0) / S * S;  // the last row boundary within the budget
+      if (next <= cur) {  // one row is past the budget: that row alone
+        const PhxTensor& C = P.tab[phx_entry(P, cur)];
+        next = C.item0 + ((cur - C.item0) / C.stride + 1) * (int64_t)C.stride;
+      }
+      next = std::min(next, hi);
+    }
+    b.push_back(next);
+    cur = next;
+  }
+  return b;
+}
+
 // element runs of whole Philox rows (phx_boundary)
 void phx_census(const PhxGeo& P, int nt, int shard, int nshards, int64_t* word_range, int64_t* written) {
   const int64_t lo = phx_boundary(P, shard, nshards), hi = phx_boundary(P, shard + 1, nshards);

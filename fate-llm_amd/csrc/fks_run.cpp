@@ -523,6 +523,100 @@ void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fl
   }
 }
 
+// ---- seed-basis expansion (torch_rocm stream) ----
+// fks_expand_multi's workspace, one per-call table uploaded in stream order: the outputs' pieces
+// ([nvec][entries] ProjVecEntry, a tensor past 2^31 bytes has several entries), the seeds ([k] u64),
+// then the coefficients as f32, per batch of kExpMaxVec outputs a block [k][outputs of the batch]
+struct ExpandWs {
+  size_t seeds_off = 0, coef_off = 0, total = 0;
+};
+static ExpandWs expand_ws(int entries, int k, int nvec) {
+  ExpandWs W;
+  W.seeds_off = project_table_bytes(entries, nvec);
+  W.coef_off = W.seeds_off + align_up(sizeof(uint64_t) * (size_t)std::max(k, 0), 256);
+  W.total = W.coef_off + align_up(sizeof(float) * (size_t)std::max(k, 0) * (size_t)std::max(nvec, 0), 256);
+  return W;
+}
+
+size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec) {
+  return expand_ws(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).nt, k, nvec).total;
+}
+
+// FKS_EXPAND_WORK (read per call): the seed-elements of one launch, an A/B and test switch
+int64_t expand_launch_work() {
+  if (const char* e = std::getenv("FKS_EXPAND_WORK")) {
+    char* end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    if (end != e && v > 0) return (int64_t)v;
+  }
+  return kExpLaunchWork;
+}
+
+void expand(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+            const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream) {
+  // the geometry on the host first: the workspace is checked before anything is allocated or launched
+  const DevCaps dc = device_caps();
+  const PhxGeo geo = phx_geometry(t, nt, nullptr, 0, dc.max_grid);
+  const int64_t lo = phx_boundary(geo, shard, nshards), hi = phx_boundary(geo, shard + 1, nshards);
+  if (lo >= hi) return;  // nothing in this shard
+  const ExpandWs W = expand_ws(geo.nt, k, nvec);
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < W.total)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(W.total) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  const std::vector<int64_t> cuts = phx_expand_cuts(geo, lo, hi, k, expand_launch_work());
+  thread_local std::vector<uint8_t> host;  // the upload's source outlives the call
+  host.assign(W.total, 0);
+  {
+    std::vector<int64_t> start((size_t)nt, 0);  // the tensors' first elements in the concatenation
+    for (int i = 1; i < nt; i++) start[i] = start[i - 1] + t[i - 1].numel;
+    ProjVecEntry* ot = reinterpret_cast<ProjVecEntry*>(host.data());
+    for (int m = 0; m < nvec; m++)
+      for (int e = 0; e < geo.nt; e++) {
+        const int i = geo.tensor_of[e];
+        const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
+        ProjVecEntry& x = ot[(size_t)m * (size_t)geo.nt + (size_t)e];
+        x.ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)(geo.elem0[e] - start[i]) * elem_size(v.dtype);
+        x.dtype = v.dtype;
+        x.flags = (x.ptr % 16u) == 0 ? kPhxP16 : 0u;
+      }
+    if (k > 0) std::memcpy(host.data() + W.seeds_off, seeds, sizeof(uint64_t) * (size_t)k);
+    float* c = reinterpret_cast<float*>(host.data() + W.coef_off);
+    for (int m0 = 0; m0 < nvec; m0 += kExpMaxVec) {
+      const int nv = std::min(kExpMaxVec, nvec - m0);
+      float* blk = c + (size_t)k * (size_t)m0;
+      for (int s = 0; s < k; s++)
+        for (int m = 0; m < nv; m++) blk[(size_t)s * nv + m] = (float)coefs[(size_t)(m0 + m) * (size_t)k + s];
+    }
+  }
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = get_phx_plan(t, nt, nullptr, 0, dc);
+  if (P->nt != geo.nt) throw Error(-FKS_EINVAL, "torch_rocm plan does not match the call's geometry");
+  check_hip(hipMemcpyAsync(workspace, host.data(), W.total, hipMemcpyHostToDevice, (hipStream_t)stream),
+            "hipMemcpyAsync");
+  const uint8_t* ws = static_cast<const uint8_t*>(workspace);
+  for (int m0 = 0; m0 < nvec; m0 += kExpMaxVec) {  // batches of outputs over the same seeds
+    ExpandArgs a{};
+    a.t = static_cast<const PhxTensor*>(P->dev);
+    a.nt = P->nt;
+    a.nvec = std::min(kExpMaxVec, nvec - m0);
+    a.ot = reinterpret_cast<const ProjVecEntry*>(ws) + (size_t)m0 * (size_t)P->nt;
+    a.seeds = reinterpret_cast<const uint64_t*>(ws + W.seeds_off);
+    a.coef = reinterpret_cast<const float*>(ws + W.coef_off) + (size_t)k * (size_t)m0;
+    a.nseeds = k;
+    for (int m = 0; m < a.nvec; m++) {
+      const double beta = betas ? betas[m0 + m] : 0.0;
+      a.beta[m] = (float)beta;
+      a.read_old |= beta != 0.0 ? 1u << m : 0u;
+    }
+    for (size_t c = 0; c + 1 < cuts.size(); c++) {  // launches of at most expand_launch_work() seed-elements
+      a.item_lo = cuts[c];
+      a.item_hi = cuts[c + 1];
+      check_launch(timed(0, stream, [&] { return launch_expand_multi(a, stream); }), "fks_expand_multi_kernel",
+                   "bad arguments");
+    }
+  }
+}
+
 // ---- seed-basis projection (CPU generator's stream) ----
 // The plan fks_delta_accumulate launches for `vec` as its delta buffer; per pass of
 // kMaxSeedsPerPass seeds the regular jump, one launch per dtype with fast segments, the irregular

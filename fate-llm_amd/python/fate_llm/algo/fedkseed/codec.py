@@ -814,6 +814,95 @@ def _project_in_place(specs, seeds, vectors, mode, shard, nshards) -> torch.Tens
     return out
 
 
+# outputs that share one pass of the generator in expand_multi (csrc/fks_expand.h kExpMaxVec;
+# more run in batches, with the same bits)
+EXPAND_PASS_OUTPUTS = 4
+
+
+def expand_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, outputs, betas=None, stream_mode=None,
+                 shard: int = 0, nshards: int = 1) -> None:
+    """Seed-basis expansion written in place (include/fks.h fks_expand_multi), the other direction
+    of ``project_multi``: outputs[m] = cast(betas[m] * outputs[m] + sum_s f32(coefs[m][s]) z_s) over
+    the non-frozen specs' elements that element shard ``shard`` of ``nshards`` owns
+    (``shard_range``), z_s the torch_rocm stream's draw for seeds[s] in each spec's dtype.
+    ``outputs`` is a sequence of M sequences with one tensor per spec (None for a frozen spec
+    only): each a contiguous float32 / bfloat16 / float16 tensor on the specs' device with the
+    spec's element count, of any of the three dtypes whatever the spec's, written in place and
+    once.  ``coefs`` is M x K (a flat sequence of K for M = 1); ``betas`` one number per output,
+    default all zero: with beta 0 an output is never read, so ``torch.empty`` will do.  The sum is
+    ``delta_accumulate``'s f32 fma chain in seed order, kept in registers over all K seeds: an f32
+    output with beta 0 equals ``delta_accumulate`` on a zeroed buffer bit for bit, a 2-byte output
+    that value rounded once; row m equals the one-output call bit for bit.  There is no buffer of
+    the model's size and no plan keyed on an address.  ValueError for an output that is not
+    contiguous (there is no staging copy to write back), of another dtype, device or size, for the
+    same ``data_ptr`` twice, and for a ``coefs`` shape other than M x K.  Asynchronous on the
+    current stream; draws nothing from torch's generators.  torch_rocm stream only: a call that
+    resolves to torch_cpu raises NotImplementedError (``delta_accumulate`` sums that stream into an
+    f32 buffer)."""
+    specs = list(specs)
+    outputs = [list(o) for o in outputs]
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: expand_multi() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), which "
+                                  f"delta_accumulate() sums into an f32 buffer")
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    M, n, K = len(outputs), len(specs), len(seeds)
+    c = np.asarray(coefs, dtype=np.float64)
+    if M == 1 and c.shape == (K,):
+        c = c.reshape(1, K)
+    if c.shape != (M, K) and not (M == 0 and c.size == 0):
+        raise ValueError(f"coefs must be {M} x {K} (outputs x seeds), got shape {c.shape}")
+    c = np.ascontiguousarray(c.reshape(M, K))
+    bt = np.zeros(M, dtype=np.float64) if betas is None else np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+    if bt.shape != (M,):
+        raise ValueError(f"betas: one number per output is needed: {M} outputs, {bt.size} betas")
+    seen = set()
+    for m, os_ in enumerate(outputs):  # every argument error before anything touches a device
+        if len(os_) != n:
+            raise ValueError(f"output {m}: one tensor per spec is needed: {n} specs, {len(os_)} tensors")
+        for i, (sp, o) in enumerate(zip(specs, os_)):
+            if sp.frozen:
+                continue  # ignored
+            if o is None:
+                raise ValueError(f"output {m}: spec {i} is not frozen and has no tensor")
+            if o.dtype not in _DTYPES:
+                raise ValueError(f"output {m}, spec {i}: a float32, bfloat16 or float16 tensor is needed, got {o.dtype}")
+            if o.numel() != sp.tensor.numel():
+                raise ValueError(f"output {m}, spec {i}: {sp.tensor.numel()} elements are needed, got {tuple(o.shape)}")
+            if o.device != sp.tensor.device:
+                raise ValueError(f"output {m}, spec {i}: on {o.device}, the spec is on {sp.tensor.device}")
+            if not o.is_contiguous():
+                raise ValueError(f"output {m}, spec {i}: not contiguous (outputs are written in place: there is no "
+                                 f"staging copy to write back)")
+            if o.numel():
+                if o.data_ptr() in seen:
+                    raise ValueError(f"output {m}, spec {i}: the same data_ptr is given twice")
+                seen.add(o.data_ptr())
+    b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    if b.device is None or not M:
+        return
+    s = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    oarr = (N.FksVec * max(1, M * n))()
+    for m, os_ in enumerate(outputs):
+        for i, (sp, o) in enumerate(zip(specs, os_)):
+            if sp.frozen:
+                continue  # a NULL entry
+            oarr[m * n + i].data = o.data_ptr() if o.numel() else None
+            oarr[m * n + i].dtype = _DTYPES[o.dtype]
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_expand_multi_workspace_size(ctypes.addressof(b.arr), b.n, K, M, ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_expand_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data if K else None,
+                                   c.ctypes.data if K else None, K, ctypes.addressof(oarr), bt.ctypes.data, M,
+                                   int(shard), int(nshards), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    # queued: ws goes back to torch's allocator in stream order
+
+
 # ---------------------------------------------------------------- model fingerprint (FKSD-1)
 # Every client of a round rebuilds its model from the same model_0 and the same sums, so the
 # clients' parameters must be identical -- and since FedKSeed moves no weights, nothing else

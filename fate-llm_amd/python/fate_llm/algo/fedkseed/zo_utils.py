@@ -345,6 +345,74 @@ def fit_seed_scalars_in_place(param_groups: List[dict], seeds: Sequence[int], de
     return _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode) / float(n_live)
 
 
+def _expansion_outputs(params, outputs, m=None):
+    """One output list for ``params``: the given tensors (the entry of a parameter that does not
+    require grad is dropped), or by default every parameter's ``.grad``, created as zeros in the
+    parameter's dtype where it is None."""
+    where = "" if m is None else f"output list {m}: "
+    if outputs is None:
+        outs = []
+        for p in params:
+            if not p.requires_grad:
+                outs.append(None)
+                continue
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            outs.append(p.grad)
+        return outs
+    outputs = list(outputs)
+    if len(outputs) != len(params):
+        raise ValueError(f"{where}one output per parameter: {len(params)} parameters, {len(outputs)} outputs")
+    return [o if p.requires_grad else None for p, o in zip(params, outputs)]
+
+
+def seed_expansions_(param_groups: List[dict], seeds: Sequence[int], scalar_lists, output_lists,
+                     accumulate: bool = False, stream_mode=None):
+    """``seed_expansion_`` for M outputs in one call: output_lists[m] = (or += with
+    ``accumulate``) sum_k scalar_lists[m][k] z_k.  The z of a seed are drawn once for up to four
+    outputs (codec.expand_multi); row m equals the single call bit for bit.  An entry of
+    ``output_lists`` may be None for the default (every parameter's ``.grad``).  Returns the list
+    of output lists."""
+    params = [p for g in param_groups for p in g["params"]]
+    scalar_lists = [list(c) for c in scalar_lists]
+    output_lists = list(output_lists)
+    if len(scalar_lists) != len(output_lists):
+        raise ValueError(f"one scalar list per output list: {len(output_lists)} output lists, "
+                         f"{len(scalar_lists)} scalar lists")
+    outs = [_expansion_outputs(params, o, m) for m, o in enumerate(output_lists)]
+    if not params or not outs:
+        return outs
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    betas = [1.0 if accumulate else 0.0] * len(outs)
+    detached = [[None if o is None else o.detach() for o in os_] for os_ in outs]
+    codec.expand_multi(specs, seeds, scalar_lists, detached, betas=betas, stream_mode=stream_mode)
+    return outs
+
+
+def seed_expansion_(param_groups: List[dict], seeds: Sequence[int], scalars: Sequence[float], outputs=None,
+                    accumulate: bool = False, stream_mode=None):
+    """The dense vector of (seed, scalar) pairs, sum_k scalars[k] z_k, written (or added, with
+    ``accumulate``) into ``outputs`` -- the other direction of ``seed_projections``: what
+    ``fit_seed_scalars*`` made of a dense delta, handed back as dense tensors; the zeroth-order
+    gradient estimate sum_k g_k z_k where a torch optimizer looks for it; the Z c of the residual
+    delta - Z c that shows how well a fit holds.
+
+    ``outputs``: one contiguous float32 / bfloat16 / float16 tensor per parameter of the groups,
+    in order, each with its parameter's element count and on its device, of any of the three
+    dtypes (the entry of a parameter that does not require grad is ignored and may be None);
+    default: every parameter's ``.grad``, created in the parameter's dtype where it is None -- so
+    ``torch.optim.AdamW(...).step()``, gradient clipping or accumulation follow as after a
+    backward pass.  z_k is the stream ``directional_derivative_step`` draws for seed k: every
+    parameter draws in its own dtype; those that do not require grad are frozen (drawn, not
+    written).  The sum is an f32 fma chain in seed order held in registers over all the seeds and
+    rounded once to the output's dtype (codec.expand_multi): no f32 buffer of the model's size
+    and no pass over memory per 32 seeds.  Queued on the current stream; torch's generators are
+    left alone.  torch_rocm stream only: a call that resolves to torch_cpu raises
+    NotImplementedError.  Returns the list of outputs."""
+    return seed_expansions_(param_groups, seeds, [list(scalars)], [outputs], accumulate=accumulate,
+                            stream_mode=stream_mode)[0]
+
+
 def build_seed_candidates(k, low=0, high=2**32):
     """K seed candidates drawn from the global torch generator."""
     return torch.randint(low, high, size=(k,), dtype=torch.long)

@@ -407,6 +407,53 @@ int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
                          int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
                          size_t ws_bytes, void* stream);
 
+/* ---- seed-basis expansion written in place (torch_rocm stream) ----
+ * fks_expand_multi: the other direction of fks_project_multi, Z c instead of Z^T v: nvec dense
+ * outputs, each written where it lies and in its own dtype.  outs is a HOST array of nvec x nt
+ * fks_vec entries: outs[m * nt + i].data is a DEVICE pointer to t[i].numel contiguous elements of
+ * outs[m * nt + i].dtype (FKS_F32, FKS_BF16 or FKS_F16, independent of the tensor's dtype, which
+ * still selects z), aligned to its element size only; entries of frozen and empty tensors are
+ * ignored and may be NULL.  coefs is a HOST array of nvec x k doubles, betas one of nvec doubles
+ * (NULL: all zero).  For every output m < nvec, every non-frozen tensor i and every element e that
+ * element shard `shard` of `nshards` owns (fks_project's whole Philox rows, fks_shard_census):
+ *   acc = +0.0f;  for s = 0 .. k-1 in order: acc = fmaf((float)coefs[m * k + s], z_s(i, e), acc);
+ *   out = cast(acc) if betas[m] == 0, else cast(fmaf((float)betas[m], widen(out), acc))
+ * with z_s the value fks_normal writes for seeds[s] in the tensor's dtype, cast round-to-nearest-
+ * even to the output's dtype and widen exact.  With betas[m] == 0 the old contents are never read
+ * (an uninitialised or NaN-filled output is valid); coefficients equal to zero are not skipped.
+ * The chain is fks_delta_accumulate's: an f32 output with beta 0 equals, bit for bit, the
+ * tensor's range of fks_delta_accumulate run on a zeroed buffer with the same seeds and
+ * coefficients; a bf16 / f16 output equals that range rounded once.  The sums stay in registers
+ * across all k seeds: no seed passes over memory, no intermediate rounding, no f32 buffer of the
+ * model's size, and every output is written once.  At most 4 outputs share one pass of the
+ * generator; a larger nvec runs in batches.  No element depends on another: row m of any call
+ * equals the one-output call bit for bit, however the outputs are batched and the launches cut.
+ * Frozen tensors advance the Philox offset and are not written; elements outside the shard are
+ * not touched.  lr, wd, the other flags and the tensors' own data pointers are ignored; nothing
+ * is drawn from torch's generators.  Outputs that overlap each other give undefined results.
+ * The outputs' addresses key no cached plan (one geometry-only plan per tensor list): the per-call
+ * table -- output pieces, seeds, coefficients -- travels at the front of the workspace, uploaded in
+ * stream order, the call's only host-to-device traffic.  A launch holds at most 2^37 seed-elements
+ * (whole rows; never less than one row): a long sum runs as several launches.  The environment
+ * variable FKS_EXPAND_WORK, read per call, overrides that number (an A/B and test switch).
+ * k == 0 writes +0 where betas[m] == 0; nvec == 0, nt == 0 and all-empty lists succeed.
+ * Workspace: fks_expand_multi_workspace_size (8-byte aligned).  Errors, raised from the arguments
+ * alone before any device work: nvec < 0, k < 0, a NULL seeds or coefs with k > 0, a NULL outs with
+ * nvec > 0 and nt > 0, an output dtype outside the three, a NULL or misaligned output pointer for
+ * a non-frozen, non-empty tensor, a bad shard, a NULL, misaligned or too small workspace:
+ * -FKS_EINVAL; a list without FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_delta_accumulate sums either
+ * stream into an f32 buffer).
+ * fks_expand_launch_cuts (diagnostics, tests): the item boundaries cuts[0] < ... < cuts[n - 1] of
+ * the launches a call with k seeds makes for the shard (n - 1 launches; n = 0: nothing to do);
+ * work <= 0: the call's own bound; max_grid <= 0: the current device's torch grid cap.  Writes
+ * at most cap boundaries and sets *ncuts = n.                                              */
+int fks_expand_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
+int fks_expand_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                     const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                     void* workspace, size_t ws_bytes, void* stream);
+int fks_expand_launch_cuts(const fks_tensor* t, int32_t nt, int32_t k, int32_t shard, int32_t nshards, int64_t work,
+                           int64_t max_grid, int64_t* cuts, int32_t cap, int32_t* ncuts);
+
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
