@@ -54,6 +54,15 @@ constexpr int kBsFence = 8;      // slice kernel: compiler fence after every 8 s
 #ifndef FKS_BS_FLIPMUX           // 1: the flip of the tempered planes as v_bitop3_b32 on a per-lane mask
 #define FKS_BS_FLIPMUX 1
 #endif
+// slice kernel, the fma-free wd +0 chain (kModeUpdateWdPos0, the host's choice: fks_run.cpp).  Kept as a set with it:
+// -4.1 % per launch against the parent; the fma-free chain alone gains nothing, D = 8 with it 1.1 %, D = 8 and H1
+// 2.2-2.5 % (profiles/r10_bs_pos0_ab.log)
+#ifndef FKS_BS_LOOK              // D: the table lookups (loads only) of seed k + D are issued ahead of seed k's
+#define FKS_BS_LOOK 16           // arithmetic (0: at their seed; at most 32)
+#endif
+#ifndef FKS_BS_H1                // 1: the twist's row and address arithmetic ahead of the flag poll, pinned in
+#define FKS_BS_H1 1              // VGPRs
+#endif
 #ifndef FKS_PHX_VEC_ITEMS        // torch_rocm few-seed kernel: work items per thread (8; A/B: 4), see
 #define FKS_PHX_VEC_ITEMS 8      // kPhxVec in fks_kern_philox.h
 #endif
@@ -199,7 +208,7 @@ int launch_apply_bs(const ApplyBsArgs& a, void* stream) {
     return -FKS_EINVAL;
   int e = ensure_tables();
   if (e) return e;
-  return dispatch(IntList<kModeUpdate, kModeUpdateWd, kModeUpdateNoWd, kModeUpdateWd0, kModeDelta>{}, a.mode,
+  return dispatch(IntList<kModeUpdate, kModeUpdateWd, kModeUpdateNoWd, kModeUpdateWd0, kModeUpdateWdPos0, kModeDelta>{}, a.mode,
                   [&](auto m) { return launch_apply_bs_t<decltype(m)::value>(a, stream); });
 }
 

@@ -88,6 +88,10 @@ struct PlanInfo {
   int wd_mode[3] = {kModeUpdate, kModeUpdate, kModeUpdate};  // kModeUpdateWd / NoWd when uniform
   bool have_reg = false, have_irr = false;
   bool have_bs = false;  // bf16 fast segments with their slice-kernel plan (non-small calls)
+  // the bf16 fast segments' analogue of PhxPlan::wd_pos0 / max_lr: every one of them has wd = +0.0
+  // exactly and a finite lr (the slice kernel's kModeUpdateWdPos0 candidate), and max |lr| over them
+  bool bs_wd_pos0 = false;
+  float bs_max_lr = 0.0f;
   uint64_t chunk_hash = 0;  // the chunk starts (regular + irregular): what a seed's windows depend on
   int64_t reg_lo = 0, reg_hi = 0;  // MT blocks [reg_lo, reg_hi) the regular chunks cover
   uint64_t bf16_hash = 0;  // the bf16 segments' stream ranges: which blocks a z-index store covers

@@ -156,7 +156,9 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
 
   // The wd 0 chain's task path without lane-mask selects and neighbour exchanges, each lever
   // with its switch (fks_device.hip; measured in profiles/r09_bs_taskpath_ab.log)
-  constexpr bool kWd0 = MODE == kModeUpdateWd0;
+  // (kModeUpdateWdPos0 is the same chain without the tail's fma: the host chose it, fks_run.cpp)
+  constexpr bool kPos0 = MODE == kModeUpdateWdPos0;
+  constexpr bool kWd0 = MODE == kModeUpdateWd0 || kPos0;
   constexpr bool kD16 = kWd0 && FKS_BS_D16 != 0;          // parameters as 16-bit halves, no pair exchange
   constexpr bool kG32 = kWd0 && FKS_BS_G32 != 0;          // two seeds' g per SGPR pair
   constexpr bool kRowMin = kWd0 && FKS_BS_ROWMIN != 0;    // row indices wrapped by unsigned min
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // carried from task to task (next_row()).  The other chains keep the 64-bit form: with the
   // 32-bit one the weight-decay chain measured 0.4 % and the no-wd chain 0.6 % slower
   // (profiles/r07_bs_colimit_ab.log, profiles/r07_bench_parent_vs_v1all.log).
-  constexpr bool kInc = MODE == kModeUpdateWd0;
+  constexpr bool kInc = kWd0;
   int seg_lo = INT32_MAX, seg_hi = INT32_MAX;
   uint64_t seg_org = 0;
   auto load_seg = [&]() {
@@ -294,6 +296,29 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     row += kRowStep;
     if (row >= kMtN) row -= kMtN;
   };
+  // FKS_BS_H1 (the fma-free wd +0 chain): the row indices and LDS addresses of a task's twist depend
+  // on the carried row only, not on the hand-off flag: task() computes them BEFORE it polls the flag
+  // and pins them in VGPRs, so that the serial section between two flag values starts with its loads
+  // (about 26 VALU instructions at priority 2 leave it).
+  // (FKS_BS_H2, measured and removed: U31 and V of chunk arrays 0 and 1 loaded once the flag shows task
+  // n - 4 twisted, ahead of the poll for task n - 1 -- those rows were last written by tasks n - 5 and
+  // n - 4 -- was bit-exact and 4 % SLOWER on top of H1: profiles/r10_bs_pos0_ab.log)
+  struct TwAddr { uint32_t av1, am1, au1, av2, am2, au2, sa, sb; };
+  constexpr bool kH1 = kPos0 && kRowMin && FKS_BS_H1 != 0;
+  TwAddr pre{};
+  auto tw_pre = [&]() {
+    const uint32_t ia = (uint32_t)row + rofa, ib = (uint32_t)row + rofb;
+    pre.av1 = sbase + 16u * wrap(ia + 1u);
+    pre.am1 = sbase + 16u * wrap(ia + kMtM);
+    pre.au1 = sbase + 7u * kBsChunkBytes + 16u * ia + 12u;
+    pre.av2 = sbase + 16u * wrap(ib + 1u);
+    pre.am2 = sbase + 16u * wrap(ib + kMtM);
+    pre.au2 = sbase + 7u * kBsChunkBytes + 16u * ib + 12u;
+    pre.sa = sbase + 16u * ia;
+    pre.sb = sbase + 16u * ib;
+    asm volatile("" : "+v"(pre.av1), "+v"(pre.am1), "+v"(pre.au1), "+v"(pre.av2), "+v"(pre.am2), "+v"(pre.au2),
+                 "+v"(pre.sa), "+v"(pre.sb));
+  };
   auto twist = [&](const int n, uint32_t (&oa)[8], uint32_t (&ob)[8]) {
     const int u1 = kBsTaskWords * n + toff;
     const bool valid = u1 < nwords;
@@ -310,6 +335,10 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     uint32_t av1, am1, au1, av2, am2, au2;
     rows(ia, av1, am1, au1);
     rows(ib, av2, am2, au2);
+    if (kH1) {
+      av1 = pre.av1; am1 = pre.am1; au1 = pre.au1;
+      av2 = pre.av2; am2 = pre.am2; au2 = pre.au2;
+    }
     uint32_t M1[32], M2[32];  // the new rows
     const uint32_t U1 = lds_u32((int)au1), U2 = lds_u32((int)au2);
     // (issuing all 34 loads of the task at once -- 164 VGPRs -- measured 5 % slower per
@@ -343,8 +372,8 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
         M2[b] = am ? bs::xor3(Mb[t], xb, v0b) : (Mb[t] ^ xb);
       }
       if (valid) {
-        lds_st4(sbase + 16u * (uint32_t)ia + q * kBsChunkBytes, u32x4_t{M1[4 * q], M1[4 * q + 1], M1[4 * q + 2], M1[4 * q + 3]});
-        lds_st4(sbase + 16u * (uint32_t)ib + q * kBsChunkBytes, u32x4_t{M2[4 * q], M2[4 * q + 1], M2[4 * q + 2], M2[4 * q + 3]});
+        lds_st4((kH1 ? pre.sa : sbase + 16u * (uint32_t)ia) + q * kBsChunkBytes, u32x4_t{M1[4 * q], M1[4 * q + 1], M1[4 * q + 2], M1[4 * q + 3]});
+        lds_st4((kH1 ? pre.sb : sbase + 16u * (uint32_t)ib) + q * kBsChunkBytes, u32x4_t{M2[4 * q], M2[4 * q + 1], M2[4 * q + 2], M2[4 * q + 3]});
       }
       va = va2; vb = vb2; ma = ma2; mb = mb2;
     }
@@ -405,6 +434,16 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
       p.x = ST::cvt(odd ? got : keep);
       p.y = ST::cvt(odd ? keep : got);
     }
+    if (kPos0) {
+      // The chain without the tail's fma (apply_tail: t = gz) needs a +-inf parameter to be the
+      // NaN the fma form makes of it at the first seed (0 * inf).  One packed fma(0, p, p) per
+      // task does that with the same instruction, so with the same bits: inf gives the default
+      // NaN, a NaN comes out quieted with its sign and payload (as fma(wd, p, gz) leaves it, and
+      // every later p - w keeps it), and a finite p, zeros of either sign and denormals included,
+      // comes out as itself (0 * p is a zero of p's sign, and p + that zero is p).
+      const f32x2_t zero = {0.0f, 0.0f};
+      p = __builtin_elementwise_fma(zero, p, p);
+    }
     auto z_of = [&](const int k) __attribute__((always_inline)) -> f32x2_t {
       // (all 32 R reads through the vector-memory path, each issued at its seed and waited
       // for there: 13 % slower, profiles/r04rg_r_global_ab.log.  R as bf16, two entries per
@@ -415,27 +454,60 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
       const f32x2_t cs = lds_f32x2(1024u + bs_index<3>(ob[k & 7], k >> 3));
       return rnd2<FKS_BF16>(__builtin_elementwise_fma(rr, cs, zero));
     };
+#if FKS_BS_LOOK > 0
+    // FKS_BS_LOOK = D > 0 (the fma-free wd +0 chain): a rolling window of D seeds' lookups, loads
+    // only -- those of seeds 0..D-1 issued before the seed loop, those of seed k + D in iteration k
+    // ahead of seed k's arithmetic -- so that a seed's LDS round trip passes behind D seeds' VALU
+    // work.  Plain loads: the compiler counts lgkmcnt.
+    constexpr int kLook = kPos0 ? FKS_BS_LOOK : 0;
+    static_assert(kLook <= kBsSeeds, "FKS_BS_LOOK");
+    float wr[kLook + 1];
+    f32x2_t wcs[kLook + 1];
+    auto look = [&](const int k, const int s) __attribute__((always_inline)) {
+      wr[s] = rv_slot(k) >= 0 ? rv[rv_slot(k)] : lds_f32(bs_index<2>(oa[k & 7], k >> 3));
+      wcs[s] = lds_f32x2(1024u + bs_index<3>(ob[k & 7], k >> 3));
+    };
+#pragma unroll
+    for (int k = 0; k < kLook; k++) {
+      wr[k] = 0.0f;
+      wcs[k] = f32x2_t{0.0f, 0.0f};
+      if (FULL || k < nseeds) look(k, k);
+    }
+    auto z_la = [&](const int k) __attribute__((always_inline)) -> f32x2_t {
+      const int s = k % (kLook > 0 ? kLook : 1);
+      const f32x2_t rr = {wr[s], wr[s]}, zero = {0.0f, 0.0f}, cs = wcs[s];
+      if (k + kLook < kBsSeeds && (FULL || k + kLook < nseeds)) {
+        look(k + kLook, s);
+      }
+      return rnd2<FKS_BF16>(__builtin_elementwise_fma(rr, cs, zero));
+    };
+#define FKS_BS_Z(k) (kLook > 0 ? z_la(k) : z_of(k))
+#else
+#define FKS_BS_Z(k) z_of(k)
+#endif
     // (issuing seed k+1's lookups, z and g z ahead of seed k's p-dependent tail, which
     // removes the wait state between the tail's dependent packed ops, measured 1 % slower:
     // profiles/r04d_pipe_ab.log; dropping the wd0 tail's fma -- t = gz for wd = +0 and a
     // finite p, with the chain redone exactly for the lanes that end non-finite -- issues one
     // packed op per element pair and seed fewer but measured 1.5 % slower, its lr*gz waiting
-    // on gz's conversions: profiles/r04o_wd0_nofma_ab.log)
+    // on gz's conversions: profiles/r04o_wd0_nofma_ab.log.  The host-decided form, kModeUpdateWdPos0,
+    // has no redo path; alone it gains nothing either, with the look-ahead window it does: §10 round 10)
     {
 #pragma unroll
       for (int k = 0; k < kBsSeeds; k++) {
         if (FULL || k < nseeds) {
           if (kG32)  // apply_pair's statements with g z from the shared SGPR pair
-            p = apply_tail<FKS_BF16, MODE>(p, rnd2<FKS_BF16>(k & 1 ? pk_mul_half<1>(gg[k >> 1], z_of(k)) : pk_mul_half<0>(gg[k >> 1], z_of(k))),
+            p = apply_tail<FKS_BF16, MODE>(p, rnd2<FKS_BF16>(k & 1 ? pk_mul_half<1>(gg[k >> 1], FKS_BS_Z(k)) : pk_mul_half<0>(gg[k >> 1], FKS_BS_Z(k))),
                                            sl.lr, sl.wd, sl.wdf != 0);
           else
-            p = apply_pair<FKS_BF16, MODE>(p, z_of(k), gk[k], sl.lr, sl.wd, sl.wdf != 0, 0.0f);
+            p = apply_pair<FKS_BF16, MODE>(p, FKS_BS_Z(k), gk[k], sl.lr, sl.wd, sl.wdf != 0, 0.0f);
         }
         // the lookups of one byte column (8 seeds) at a time: hoisting all 64 table reads
         // ahead of the chain would spill
         if ((k % kBsFence) == kBsFence - 1) asm volatile("" ::: "memory");
       }
     }
+#undef FKS_BS_Z
     if (kD16) {  // p is bf16-exact: the high halves are the elements
       Traits<FKS_BF16>::store_hi(sl.addr, __float_as_uint(p.x));
       Traits<FKS_BF16>::store_hi(sl.addr + 16, __float_as_uint(p.y));
@@ -487,6 +559,7 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   auto task = [&](const int n, const Slot& sl, Slot& nx) {
     uint32_t oa[8], ob[8];
     if (kLag && ordered && half == 0) await_applied(n - FKS_BS_LAG);
+    if (kH1) tw_pre();
     __builtin_amdgcn_s_setprio(2);
     while (__builtin_amdgcn_readfirstlane(bs_flag_load(flag)) < (uint32_t)n) __builtin_amdgcn_s_sleep(0);
     asm volatile("" ::: "memory");

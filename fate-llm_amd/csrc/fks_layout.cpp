@@ -371,6 +371,13 @@ PlanImage plan_image(const fks_tensor* t, int nt, const double* scales, uint64_t
     C.wd_mode[d] = wd_form(L.segs[d], d != FKS_F32 || kWd0F32Mode);
     segs.insert(segs.end(), L.segs[d].begin(), L.segs[d].end());
   }
+  C.bs_wd_pos0 = C.wd_mode[FKS_BF16] == kModeUpdateWd0;
+  for (const DevSeg& sg : L.segs[FKS_BF16]) {
+    uint32_t wb;
+    std::memcpy(&wb, &sg.wd, 4);
+    C.bs_wd_pos0 = C.bs_wd_pos0 && wb == 0u && std::isfinite(sg.lr);
+    C.bs_max_lr = std::max(C.bs_max_lr, std::fabs(sg.lr));
+  }
   put(C.H.off_polys, polys);
   put(C.H.off_cb, cb);
   put(C.H.off_ipolys, ipolys);

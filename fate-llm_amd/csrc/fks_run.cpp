@@ -216,6 +216,20 @@ void run(const fks_tensor* t, int nt, const uint64_t* seeds, const double* value
     // attached (fks_jwin_attach): a seed already there skips its jump
     JWin* J = (slices == 2 && k > kBsSeeds) ? jw_cache(stream, C->bs_hash, C->Z.bs_chunks / kBsChunksPerWg) : nullptr;
     RecordAfter j_after{J ? &J->b : nullptr, stream, J};
+    // kModeUpdateWdPos0 under run_philox's conditions (fks_internal.h): every bf16 fast segment has
+    // wd = +0.0 and a finite lr, and |lr g z| stays <= 1e30 for every seed of the call (|z| <= 6.67
+    // bounds the bf16 table's radii too).  FKS_BS_KEEP_WD_FMA=1 keeps the fma form (tests, A/B).
+    int bs_mode = mode == kModeUpdate ? C->wd_mode[FKS_BF16] : mode;
+    if (bs_mode == kModeUpdateWd0 && C->bs_wd_pos0 && !env_on("FKS_BS_KEEP_WD_FMA")) {
+      double gmax = 0.0;
+      bool finite = std::isfinite((double)C->bs_max_lr);
+      for (int j = 0; j < k && finite; j++) {
+        const float g = gval(j, FKS_BF16);
+        finite = finite && std::isfinite(g);
+        gmax = std::max(gmax, (double)std::fabs(g));
+      }
+      if (finite && gmax * 6.67 <= 1e37 && gmax * 6.67 * (double)C->bs_max_lr <= 1e30) bs_mode = kModeUpdateWdPos0;
+    }
     for (int s0 = 0; s0 < k; s0 += per_pass) {
       const int nb = std::min(per_pass, k - s0);
       // > 32 seeds: two slices per chunk pair (jumps to every other plan boundary);
@@ -243,7 +257,7 @@ void run(const fks_tensor* t, int nt, const uint64_t* seeds, const double* value
       ba.nchunks = nch;
       ba.split = split ? 1 : 0;
       ba.nseeds = nb;
-      ba.mode = mode == kModeUpdate ? C->wd_mode[FKS_BF16] : mode;
+      ba.mode = bs_mode;
       check_launch(timed(0, stream, [&] { return launch_apply_bs(ba, stream); }), "fks_apply_bs_kernel");
     }
     (void)j_after.record();
