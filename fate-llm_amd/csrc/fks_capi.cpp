@@ -193,8 +193,9 @@ static void expand_check_stream(const fks_tensor* t, int nt) {
   if (nt == 0 || rocm_stream(t, nt)) return;
   throw Error(-FKS_ENOTSUP, std::string("fks_expand_multi: the torch_cpu stream (the CPU generator's MT19937 stream") +
                                 (libm_flavour(t, nt) ? ", FKS_LIBM flavour" : "") +
-                                ") is not supported; expansion is built for FKS_STREAM_ROCM (torch_rocm) only, "
-                                "fks_delta_accumulate sums either stream into an f32 buffer");
+                                ") is not supported here; fks_expand_multi takes FKS_STREAM_ROCM (torch_rocm) lists, "
+                                "fks_expand_mt_multi is the call for this stream (fks_delta_accumulate sums either "
+                                "stream into an f32 buffer)");
 }
 
 int fks_expand_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes) {
@@ -321,6 +322,51 @@ int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
     project_mt_multi_check_stream(t, nt);
     if (k == 0 || nvec == 0) return;
     project_mt_multi(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
+// ---- seed-basis expansion (CPU generator's stream) ----
+static void expand_mt_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_expand_mt_multi: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_expand_multi is the call for that stream");
+}
+
+int fks_expand_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, int32_t shard,
+                                       int32_t nshards, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    check_shard(shard, nshards);
+    expand_mt_check_stream(t, nt);
+    *bytes = expand_mt_ws(t, nt, k, nvec, shard, nshards, device_cu_count()).total;
+  });
+}
+
+int fks_expand_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                        const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                        void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    if (nvec < 0) throw Error(-FKS_EINVAL, "negative output count");
+    check_shard(shard, nshards);
+    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+    if (k > 0 && nvec > 0 && !coefs) throw Error(-FKS_EINVAL, "null coefficient array");
+    if (nvec > 0 && nt > 0 && !outs) throw Error(-FKS_EINVAL, "null output list");
+    for (int m = 0; m < nvec; m++)
+      for (int i = 0; i < nt; i++) {
+        if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
+        const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
+        if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
+          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad output dtype " +
+                                       std::to_string(v.dtype));
+        if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
+          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) +
+                                       ": null or misaligned output pointer");
+      }
+    expand_mt_check_stream(t, nt);
+    if (nvec == 0 || nt == 0) return;
+    expand_mt_multi(t, nt, seeds, coefs, k, outs, betas, nvec, shard, nshards, workspace, ws_bytes, stream);
   });
 }
 

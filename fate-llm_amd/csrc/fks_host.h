@@ -12,6 +12,7 @@
 #include "fks_internal.h"
 #include "fks_project_mt.h"
 #include "fks_expand.h"
+#include "fks_expand_mt.h"
 
 namespace fks {
 
@@ -124,6 +125,18 @@ struct ProjMtMultiWs {
   int pass_vec = 0;        // vectors per pass: min(nvec, kProjMtMaxVec), at least 1
 };
 ProjMtMultiWs project_mt_multi_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
+// fks_expand_mt_multi's, for one shard's plan: [output table: nvec x entries pieces | generator
+// windows of one pass | sink 4 KB | f32 staging area of one output].  The staging area exists for
+// k > kMaxSeedsPerPass only and holds the elements of the concatenation from the first to the last
+// one any descriptor of the shard's clipped layout touches.
+struct ExpMtWs {
+  bool work = false;       // the shard holds an element of a non-frozen tensor
+  int entries = 0;         // descriptors of the shard's plan: fast segments + runs + single elements
+  int reg_chunks = 0, irr_chunks = 0;  // chunks of the plan's launches, at most
+  int64_t elem_lo = 0, elem_hi = 0;    // the span [elem_lo, elem_hi) of the concatenation the shard touches
+  size_t win_off = 0, sink_off = 0, stage_off = 0, stage_bytes = 0, total = 0;
+};
+ExpMtWs expand_mt_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -316,5 +329,9 @@ int64_t expand_launch_work();  // kExpLaunchWork, or FKS_EXPAND_WORK where it is
 size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec);
 void expand(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
             const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream);
+// fks_expand_mt_multi: the same on the CPU generator's stream, over the geometry-only plan
+void expand_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+                     const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes,
+                     void* stream);
 
 }  // namespace fks

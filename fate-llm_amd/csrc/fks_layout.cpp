@@ -316,6 +316,50 @@ ProjMtMultiWs project_mt_multi_ws(const fks_tensor* t, int nt, int k, int nvec, 
   return w;
 }
 
+// fks_expand_mt_multi's workspace: the per-call table of output pieces in front, as
+// fks_project_mt_multi's, then the windows of one pass, the sink, and for k > kMaxSeedsPerPass
+// the f32 staging area of one output: 4 bytes per element of the span of the concatenation that
+// the shard's clipped layout touches (a run's elements at or past its limit are not touched).
+ExpMtWs expand_mt_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus) {
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  ExpMtWs w;
+  int64_t lo = INT64_MAX, hi = 0;
+  auto touch = [&](uint64_t ptr, int64_t n) {  // elements [e, e + n) under a descriptor at ptr
+    if (n <= 0) return;
+    const int64_t e = (int64_t)((ptr - kProjMtGeoBase) / 4);
+    lo = std::min(lo, e);
+    hi = std::max(hi, e + n);
+  };
+  bool reg = false;
+  for (int d = 0; d < 3; d++)
+    for (const DevSeg& s : L.segs[d]) {
+      reg = true;
+      touch(s.ptr, s.numel);
+    }
+  for (const DevRun& R : L.runs) touch(R.ptr, std::min(R.limit, R.numel));
+  for (const DevTiny& T : L.tiny) touch(T.ptr, 1);
+  if (reg) w.reg_chunks = plan_nchunks(std::max<int64_t>(1, br.hi - br.lo), false, cus);
+  int64_t covered = 0;  // owner blocks of the irregular work
+  for (auto& x : irregular_owner_intervals(L)) covered += x.second - x.first;
+  if (covered) w.irr_chunks = plan_nchunks(covered, false, cus);
+  w.work = reg || covered > 0;
+  w.entries = nsegs_total(L) + (int)L.runs.size() + (int)L.tiny.size();
+  if (lo < hi) {
+    w.elem_lo = lo;
+    w.elem_hi = hi;
+  }
+  w.win_off = align_up(sizeof(ProjMtVecEntry) * (size_t)std::max(nvec, 0) * (size_t)w.entries, 256);
+  const size_t win = sizeof(uint32_t) * kMtN * (size_t)std::max(0, std::min(k, kMaxSeedsPerPass)) *
+                     (size_t)std::max({w.reg_chunks, w.irr_chunks, 1});
+  w.sink_off = w.win_off + align_up(win, 256);
+  w.stage_off = w.sink_off + kWsStatesOff;
+  w.stage_bytes = k > kMaxSeedsPerPass ? sizeof(float) * (size_t)(w.elem_hi - w.elem_lo) : 0;
+  w.total = w.stage_off + w.stage_bytes;
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

@@ -832,4 +832,122 @@ void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k,
   }
 }
 
+// ---- seed-basis expansion (CPU generator's stream) ----
+// project_mt_multi's frame run the other way: the geometry-only plan, the per-call table of the
+// outputs' pieces at the front of the workspace, then per output the passes of kMaxSeedsPerPass
+// seeds -- the regular jump, one launch per dtype with fast segments, the irregular jump and
+// launch.  A call of more than one pass keeps one output's f32 sums in the staging area at the
+// back of the workspace between its passes (fks_expand_mt.h); k == 0 is one pass without seeds.
+void expand_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+                     const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes,
+                     void* stream) {
+  // the layout on the host first: the workspace is checked before anything is allocated or launched
+  const DevCaps dc = device_caps();
+  const ExpMtWs W = expand_mt_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.work) return;  // nothing in this shard
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < W.total)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(W.total) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  // the table on the host, from the layout the plan is built from
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  clip_segments(L, shard_blocks(L.stream_len, shard, nshards));
+  const size_t nsegs = L.segs[0].size() + L.segs[1].size() + L.segs[2].size();
+  const size_t E = nsegs + L.runs.size() + L.tiny.size();
+  if (E != (size_t)W.entries) throw Error(-FKS_EINVAL, "the layout does not match the call's workspace layout");
+  std::vector<int64_t> start((size_t)nt, 0);  // the tensors' first elements in the concatenation
+  for (int i = 1; i < nt; i++) start[i] = start[i - 1] + t[i - 1].numel;
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  host.assign((size_t)nvec * E, ProjMtVecEntry{});
+  for (int m = 0; m < nvec; m++) {
+    ProjMtVecEntry* x = host.data() + (size_t)m * E;
+    // a descriptor of tensor i whose element 0 is element (ptr - base) / 4 of the concatenation
+    auto put = [&](int i, uint64_t ptr) {
+      const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
+      const int64_t e = (int64_t)((ptr - kProjMtGeoBase) / 4) - start[i];
+      x->ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)e * elem_size(v.dtype);
+      x->dtype = v.dtype;
+      x++;
+    };
+    for (int d = 0; d < 3; d++)
+      for (size_t j = 0; j < L.segs[d].size(); j++) put(L.seg_tensor[d][j], L.segs[d][j].ptr);
+    for (size_t j = 0; j < L.runs.size(); j++) put(L.run_tensor[j], L.runs[j].ptr);
+    for (size_t j = 0; j < L.tiny.size(); j++) put(L.tiny_tensor[j], L.tiny[j].ptr);
+  }
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  bool same = (size_t)C->Z.nsegs == nsegs && (size_t)C->Z.nruns == L.runs.size() && (size_t)C->Z.ntiny == L.tiny.size();
+  for (int d = 0; d < 3; d++) same = same && (size_t)C->nsegs[d] == L.segs[d].size();
+  if (!same || (!C->have_reg && !C->have_irr) || (C->have_reg && C->Z.reg_chunks > W.reg_chunks) ||
+      (C->have_irr && C->Z.irr_chunks > W.irr_chunks))
+    throw Error(-FKS_EINVAL, "the plan does not match the call's workspace layout");
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + W.win_off);
+  const uint64_t* sink = reinterpret_cast<const uint64_t*>(ws + W.sink_off);
+  const int passes = std::max(1, (k + kMaxSeedsPerPass - 1) / kMaxSeedsPerPass);
+  for (int m = 0; m < nvec; m++) {  // one output per pass of the generator
+    const ProjMtVecEntry* tab = table + (size_t)m * E;
+    const double beta = betas ? betas[m] : 0.0;
+    for (int p = 0; p < passes; p++) {
+      const int s0 = p * kMaxSeedsPerPass, nb = std::min(kMaxSeedsPerPass, k - s0);
+      ExpMtPass ps{};
+      for (int j = 0; j < nb; j++) ps.g[j] = (float)coefs[(size_t)m * (size_t)k + (size_t)(s0 + j)];
+      ps.stage_bias = (uint64_t)(uintptr_t)(ws + W.stage_off) - kProjMtGeoBase - 4u * (uint64_t)W.elem_lo;
+      ps.beta = (float)beta;
+      ps.nseeds = nb;
+      ps.carry_in = p > 0 ? 1 : 0;
+      ps.to_stage = p + 1 < passes ? 1 : 0;
+      ps.read_old = beta != 0.0 ? 1 : 0;
+      if (C->have_reg) {
+        JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_polys, C->H.off_cb, states, C->Z.reg_chunks);
+        ja.chunks_per_wg = jump_chunks_per_wg(std::max(nb, 1), C->Z.reg_chunks, dc.cus);
+        if (nb > 0) check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+        size_t seg0 = 0;  // the dtype's first segment in the table row
+        for (int d = 0; d < 3; d++) {
+          const size_t first = seg0;
+          seg0 += (size_t)C->nsegs[d];
+          if (!C->nsegs[d]) continue;
+          ExpMtArgs ea{};
+          ea.p = ps;
+          ea.states = states;
+          ea.segs = reinterpret_cast<const DevSeg*>(hdr + C->seg_off[d]);
+          ea.chunk_block = ja.chunk_block;
+          ea.sink = sink;
+          ea.pv = tab + first;
+          ea.nsegs = C->nsegs[d];
+          ea.nchunks = C->Z.reg_chunks;
+          const int dd = (d == FKS_F32 && libm) ? kDtF32Libm : d;
+          check_launch(timed(0, stream, [&] { return launch_expand_mt(dd, ea, stream); }), "fks_expand_mt_kernel",
+                       "bad arguments");
+        }
+      }
+      if (C->have_irr) {
+        JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_ipolys, C->H.off_ilo, states, C->Z.irr_chunks);
+        ja.chunks_per_wg = std::max(1, std::min(32, C->Z.irr_chunks));
+        if (nb > 0) check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+        ExpMtIrrArgs ia{};
+        ia.p = ps;
+        ia.states = states;
+        ia.runs = reinterpret_cast<const DevRun*>(hdr + C->H.off_runs);
+        ia.tiny = reinterpret_cast<const DevTiny*>(hdr + C->H.off_tiny);
+        ia.chunk_lo = ja.chunk_block;
+        ia.chunk_hi = reinterpret_cast<const int64_t*>(hdr + C->H.off_ihi);
+        ia.rv = tab + nsegs;
+        ia.tv = tab + nsegs + L.runs.size();
+        ia.nruns = C->Z.nruns;
+        ia.ntiny = C->Z.ntiny;
+        ia.nchunks = C->Z.irr_chunks;
+        ia.nseeds = nb;
+        ia.libm = libm ? 1 : 0;
+        check_launch(timed(0, stream, [&] { return launch_expand_mt_irr(ia, stream); }), "fks_expand_mt_irr_kernel",
+                     "bad arguments");
+      }
+    }
+  }
+}
+
 }  // namespace fks

@@ -34,6 +34,7 @@ EXPORTED = (
     "fks_project_multi_workspace_size", "fks_project_multi", "fks_project_mt_workspace_size", "fks_project_mt",
     "fks_project_mt_multi_workspace_size", "fks_project_mt_multi",
     "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
+    "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
 )
 
 
@@ -131,6 +132,8 @@ def load():
         L.fks_expand_multi.argtypes = [P, c_i32, P, P, c_i32, P, P, c_i32, c_i32, c_i32, P, c_sz, P]
         L.fks_expand_launch_cuts.argtypes = [P, c_i32, c_i32, c_i32, c_i32, ctypes.c_int64, ctypes.c_int64, P, c_i32,
                                              ctypes.POINTER(c_i32)]
+        L.fks_expand_mt_multi_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_expand_mt_multi.argtypes = [P, c_i32, P, P, c_i32, P, P, c_i32, c_i32, c_i32, P, c_sz, P]
         for name in ("fks_workspace_size", "fks_directional_step", "fks_perturb", "fks_normal",
                      "fks_host_jump_window", "fks_host_tables", "fks_directional_step_shard",
                      "fks_stream_length", "fks_profile_begin", "fks_profile_end", "fks_shard_census", "fks_perturb_step",
@@ -141,7 +144,8 @@ def load():
                      "fks_project_workspace_size", "fks_project", "fks_project_multi_workspace_size",
                      "fks_project_multi", "fks_project_mt_workspace_size", "fks_project_mt",
                      "fks_project_mt_multi_workspace_size", "fks_project_mt_multi",
-                     "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts"):
+                     "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
+                     "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi"):
             getattr(L, name).restype = ctypes.c_int
         if L.fks_abi_version() != ABI_VERSION:
             raise OSError(f"libfks.so ABI {L.fks_abi_version()} != {ABI_VERSION}")

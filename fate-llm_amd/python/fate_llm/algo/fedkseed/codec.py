@@ -819,34 +819,9 @@ def _project_in_place(specs, seeds, vectors, mode, shard, nshards) -> torch.Tens
 EXPAND_PASS_OUTPUTS = 4
 
 
-def expand_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, outputs, betas=None, stream_mode=None,
-                 shard: int = 0, nshards: int = 1) -> None:
-    """Seed-basis expansion written in place (include/fks.h fks_expand_multi), the other direction
-    of ``project_multi``: outputs[m] = cast(betas[m] * outputs[m] + sum_s f32(coefs[m][s]) z_s) over
-    the non-frozen specs' elements that element shard ``shard`` of ``nshards`` owns
-    (``shard_range``), z_s the torch_rocm stream's draw for seeds[s] in each spec's dtype.
-    ``outputs`` is a sequence of M sequences with one tensor per spec (None for a frozen spec
-    only): each a contiguous float32 / bfloat16 / float16 tensor on the specs' device with the
-    spec's element count, of any of the three dtypes whatever the spec's, written in place and
-    once.  ``coefs`` is M x K (a flat sequence of K for M = 1); ``betas`` one number per output,
-    default all zero: with beta 0 an output is never read, so ``torch.empty`` will do.  The sum is
-    ``delta_accumulate``'s f32 fma chain in seed order, kept in registers over all K seeds: an f32
-    output with beta 0 equals ``delta_accumulate`` on a zeroed buffer bit for bit, a 2-byte output
-    that value rounded once; row m equals the one-output call bit for bit.  There is no buffer of
-    the model's size and no plan keyed on an address.  ValueError for an output that is not
-    contiguous (there is no staging copy to write back), of another dtype, device or size, for the
-    same ``data_ptr`` twice, and for a ``coefs`` shape other than M x K.  Asynchronous on the
-    current stream; draws nothing from torch's generators.  torch_rocm stream only: a call that
-    resolves to torch_cpu raises NotImplementedError (``delta_accumulate`` sums that stream into an
-    f32 buffer)."""
-    specs = list(specs)
-    outputs = [list(o) for o in outputs]
-    device = specs[0].tensor.device if specs else torch.device("cpu")
-    mode = resolve_stream_mode(device, stream_mode)
-    if mode != "torch_rocm":
-        raise NotImplementedError(f"FedKSeed codec: expand_multi() is built for the torch_rocm stream only; this call "
-                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), which "
-                                  f"delta_accumulate() sums into an f32 buffer")
+def _expand_arguments(specs, seeds, coefs, outputs, betas, shard, nshards):
+    """The argument checks expand_multi and expand_mt_multi share, made before anything touches a
+    device: returns (coefs as float64[M, K], betas as float64[M])."""
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     M, n, K = len(outputs), len(specs), len(seeds)
@@ -881,6 +856,39 @@ def expand_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, output
                 if o.data_ptr() in seen:
                     raise ValueError(f"output {m}, spec {i}: the same data_ptr is given twice")
                 seen.add(o.data_ptr())
+    return c, bt
+
+
+def expand_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, outputs, betas=None, stream_mode=None,
+                 shard: int = 0, nshards: int = 1) -> None:
+    """Seed-basis expansion written in place (include/fks.h fks_expand_multi), the other direction
+    of ``project_multi``: outputs[m] = cast(betas[m] * outputs[m] + sum_s f32(coefs[m][s]) z_s) over
+    the non-frozen specs' elements that element shard ``shard`` of ``nshards`` owns
+    (``shard_range``), z_s the torch_rocm stream's draw for seeds[s] in each spec's dtype.
+    ``outputs`` is a sequence of M sequences with one tensor per spec (None for a frozen spec
+    only): each a contiguous float32 / bfloat16 / float16 tensor on the specs' device with the
+    spec's element count, of any of the three dtypes whatever the spec's, written in place and
+    once.  ``coefs`` is M x K (a flat sequence of K for M = 1); ``betas`` one number per output,
+    default all zero: with beta 0 an output is never read, so ``torch.empty`` will do.  The sum is
+    ``delta_accumulate``'s f32 fma chain in seed order, kept in registers over all K seeds: an f32
+    output with beta 0 equals ``delta_accumulate`` on a zeroed buffer bit for bit, a 2-byte output
+    that value rounded once; row m equals the one-output call bit for bit.  There is no buffer of
+    the model's size and no plan keyed on an address.  ValueError for an output that is not
+    contiguous (there is no staging copy to write back), of another dtype, device or size, for the
+    same ``data_ptr`` twice, and for a ``coefs`` shape other than M x K.  Asynchronous on the
+    current stream; draws nothing from torch's generators.  torch_rocm stream only: a call that
+    resolves to torch_cpu raises NotImplementedError (``expand_mt_multi`` is that stream's call;
+    ``zo_utils.seed_expansion_on_stream_`` picks between the two)."""
+    specs = list(specs)
+    outputs = [list(o) for o in outputs]
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: expand_multi() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), whose in-place "
+                                  f"call is expand_mt_multi() (delta_accumulate() sums it into an f32 buffer)")
+    c, bt = _expand_arguments(specs, seeds, coefs, outputs, betas, shard, nshards)
+    M, n, K = len(outputs), len(specs), len(seeds)
     b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
     if b.device is None or not M:
         return
@@ -900,6 +908,98 @@ def expand_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, output
         N.check(L.fks_expand_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data if K else None,
                                    c.ctypes.data if K else None, K, ctypes.addressof(oarr), bt.ctypes.data, M,
                                    int(shard), int(nshards), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    # queued: ws goes back to torch's allocator in stream order
+
+
+# seeds of one pass of expand_mt_multi (csrc/fks_internal.h kMaxSeedsPerPass): more run through the staging area
+EXPAND_MT_PASS_SEEDS = 19
+# the staging budget of expand_mt_multi is at least this, and at least EXPAND_MT_STAGING_SPLIT-th
+# of the whole list's staging area: at most that many internal shards, each with its own
+# geometry-only plan in the library's 32-entry cache
+EXPAND_MT_STAGING_MIN = 1 << 30
+EXPAND_MT_STAGING_SPLIT = 8
+
+
+def _expand_mt_sizes(b: "_Batch", K: int, M: int, nshards: int):
+    """Per shard of ``nshards``: (workspace bytes, staging bytes of them) of fks_expand_mt_multi.
+    The table and the windows do not grow past one pass's seeds, so the staging area is what a
+    call of K seeds needs beyond a call of one pass.  Host arithmetic only."""
+    L = N.load()
+    out = []
+    for sh in range(nshards):
+        full, one = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        N.check(L.fks_expand_mt_multi_workspace_size(ctypes.addressof(b.arr), b.n, K, M, sh, nshards, ctypes.byref(full)))
+        N.check(L.fks_expand_mt_multi_workspace_size(ctypes.addressof(b.arr), b.n, min(K, EXPAND_MT_PASS_SEEDS), M, sh,
+                                                     nshards, ctypes.byref(one)))
+        out.append((int(full.value), int(full.value) - int(one.value)))
+    return out
+
+
+def expand_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, outputs, betas=None, shard: int = 0,
+                    nshards: int = 1, staging_bytes: Optional[int] = None) -> None:
+    """``expand_multi`` on the torch_cpu stream (include/fks.h fks_expand_mt_multi), the other
+    direction of ``project_mt_multi``: outputs[m] = cast(betas[m] * outputs[m] + sum_s f32(coefs[m][s])
+    z_s) over the non-frozen specs' elements that element shard ``shard`` of ``nshards`` owns
+    (``project_mt``'s shards), z_s the CPU generator's MT19937 draw for seeds[s] in each spec's
+    dtype -- fp32 in the process's flavour (``cpu_fp32_flavour``).  ``outputs``, ``coefs``,
+    ``betas`` and every argument check are ``expand_multi``'s, made before anything touches a
+    device; it takes no ``stream_mode`` (the stream is always torch_cpu) and has no CPU path.  The
+    sum is ``delta_accumulate``'s f32 fma chain in seed order, rounded once to the output's dtype:
+    an f32 output with beta 0 equals ``delta_accumulate(..., stream_mode="torch_cpu")`` on a zeroed
+    buffer bit for bit; row m equals the one-output call bit for bit.
+
+    Up to 19 seeds are one pass with the sums in registers: no buffer beyond the windows and the
+    table.  More seeds run in passes of 19 through an f32 staging area in the workspace, 4 bytes
+    per element of the shard.  With ``nshards == 1`` the call bounds that area itself: it splits
+    the list into the smallest number of element shards whose largest staging area fits
+    ``staging_bytes`` (default: max(1 GiB, an eighth of the whole list's staging area)) and calls
+    the library once per shard, with one workspace sized for the largest; the result does not
+    depend on the split.  A smaller explicit budget is honoured and may cost more cached plans.
+    With ``nshards > 1`` the caller has split already and ``staging_bytes`` is not consulted.
+    Asynchronous on the current stream; draws nothing from torch's generators."""
+    specs = list(specs)
+    outputs = [list(o) for o in outputs]
+    c, bt = _expand_arguments(specs, seeds, coefs, outputs, betas, shard, nshards)
+    if staging_bytes is not None and int(staging_bytes) < 0:
+        raise ValueError(f"staging_bytes {staging_bytes}")
+    M, n, K = len(outputs), len(specs), len(seeds)
+    b = _Batch(specs, "torch_cpu", stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    if b.device is None or not M:
+        return
+    s = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    oarr = (N.FksVec * max(1, M * n))()
+    for m, os_ in enumerate(outputs):
+        for i, (sp, o) in enumerate(zip(specs, os_)):
+            if sp.frozen:
+                continue  # a NULL entry
+            oarr[m * n + i].data = o.data_ptr() if o.numel() else None
+            oarr[m * n + i].dtype = _DTYPES[o.dtype]
+    L = N.load()
+    calls = [(int(shard), int(nshards))]
+    sizes = _expand_mt_sizes(b, K, M, int(nshards))[int(shard):int(shard) + 1]
+    if nshards == 1 and K > EXPAND_MT_PASS_SEEDS:
+        whole = sizes[0][1]
+        budget = (max(EXPAND_MT_STAGING_MIN, -(-whole // EXPAND_MT_STAGING_SPLIT)) if staging_bytes is None
+                  else int(staging_bytes))
+        words = ctypes.c_int64(0)
+        N.check(L.fks_stream_length(ctypes.addressof(b.arr), b.n, ctypes.byref(words)))
+        blocks = max(1, -(-int(words.value) // 624))  # shards are whole MT blocks: no finer split exists
+        ns = max(1, -(-whole // max(budget, 1)))
+        while ns > 1:  # the smallest shard count whose largest staging area fits (a shard's area shrinks with the count)
+            if ns > blocks:
+                raise ValueError(f"staging_bytes {budget}: no split of the list into element shards stages so little")
+            sizes = _expand_mt_sizes(b, K, M, ns)
+            if max(st for _, st in sizes) <= budget:
+                break
+            ns += 1
+        calls = [(sh, ns) for sh in range(ns)]
+    nbytes = max(w for w, _ in sizes)
+    with torch.cuda.device(b.device):
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=b.device)
+        for sh, ns in calls:
+            N.check(L.fks_expand_mt_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data if K else None,
+                                          c.ctypes.data if K else None, K, ctypes.addressof(oarr), bt.ctypes.data, M,
+                                          sh, ns, ws.data_ptr(), nbytes, _stream_handle(b.device)))
     # queued: ws goes back to torch's allocator in stream order
 
 

@@ -408,9 +408,52 @@ def seed_expansion_(param_groups: List[dict], seeds: Sequence[int], scalars: Seq
     rounded once to the output's dtype (codec.expand_multi): no f32 buffer of the model's size
     and no pass over memory per 32 seeds.  Queued on the current stream; torch's generators are
     left alone.  torch_rocm stream only: a call that resolves to torch_cpu raises
-    NotImplementedError.  Returns the list of outputs."""
+    NotImplementedError (``seed_expansion_on_stream_`` takes either stream).  Returns the list of
+    outputs."""
     return seed_expansions_(param_groups, seeds, [list(scalars)], [outputs], accumulate=accumulate,
                             stream_mode=stream_mode)[0]
+
+
+def seed_expansions_on_stream_(param_groups: List[dict], seeds: Sequence[int], scalar_lists, output_lists,
+                               accumulate: bool = False, stream_mode=None):
+    """``seed_expansions_`` on either stream: a call that resolves to torch_rocm takes
+    codec.expand_multi, one that resolves to torch_cpu codec.expand_mt_multi (the precedent is
+    ``seed_projections_in_place``).  Arguments, defaults (``.grad``, created in the parameter's
+    dtype where it is None; ``accumulate``) and the result are ``seed_expansions_``'s.  On
+    torch_cpu up to 19 seeds are one pass with the sums in registers -- the zeroth-order estimate
+    g z of a local step lands in ``.grad`` with no buffer beyond the generator windows --; more
+    seeds run through a bounded f32 staging area (codec.expand_mt_multi).  Row m equals the
+    single call bit for bit; torch's generators are left alone."""
+    params = [p for g in param_groups for p in g["params"]]
+    if not params or codec.resolve_stream_mode(params[0].device, stream_mode) != "torch_cpu":
+        return seed_expansions_(param_groups, seeds, scalar_lists, output_lists, accumulate=accumulate,
+                                stream_mode=stream_mode)
+    if params[0].device.type != "cuda":  # before any output is created: there is no CPU path
+        raise ValueError(f"FedKSeed codec: parameters must be on a HIP device (got {params[0].device}); "
+                         "there is no CPU path")
+    scalar_lists = [list(c) for c in scalar_lists]
+    output_lists = list(output_lists)
+    if len(scalar_lists) != len(output_lists):
+        raise ValueError(f"one scalar list per output list: {len(output_lists)} output lists, "
+                         f"{len(scalar_lists)} scalar lists")
+    outs = [_expansion_outputs(params, o, m) for m, o in enumerate(output_lists)]
+    if not outs:
+        return outs
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    betas = [1.0 if accumulate else 0.0] * len(outs)
+    detached = [[None if o is None else o.detach() for o in os_] for os_ in outs]
+    codec.expand_mt_multi(specs, seeds, scalar_lists, detached, betas=betas)
+    return outs
+
+
+def seed_expansion_on_stream_(param_groups: List[dict], seeds: Sequence[int], scalars: Sequence[float], outputs=None,
+                              accumulate: bool = False, stream_mode=None):
+    """``seed_expansion_`` on either stream (``seed_expansions_on_stream_`` for one output):
+    sum_k scalars[k] z_k written, or added with ``accumulate``, into ``outputs`` -- by default
+    every parameter's ``.grad`` --, z_k the stream the call resolves to on the parameters' device.
+    Returns the list of outputs."""
+    return seed_expansions_on_stream_(param_groups, seeds, [list(scalars)], [outputs], accumulate=accumulate,
+                                      stream_mode=stream_mode)[0]
 
 
 def build_seed_candidates(k, low=0, high=2**32):

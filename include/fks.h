@@ -441,8 +441,8 @@ int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
  * alone before any device work: nvec < 0, k < 0, a NULL seeds or coefs with k > 0, a NULL outs with
  * nvec > 0 and nt > 0, an output dtype outside the three, a NULL or misaligned output pointer for
  * a non-frozen, non-empty tensor, a bad shard, a NULL, misaligned or too small workspace:
- * -FKS_EINVAL; a list without FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_delta_accumulate sums either
- * stream into an f32 buffer).
+ * -FKS_EINVAL; a list without FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_expand_mt_multi below is the
+ * call for the CPU generator's stream; fks_delta_accumulate sums either stream into an f32 buffer).
  * fks_expand_launch_cuts (diagnostics, tests): the item boundaries cuts[0] < ... < cuts[n - 1] of
  * the launches a call with k seeds makes for the shard (n - 1 launches; n = 0: nothing to do);
  * work <= 0: the call's own bound; max_grid <= 0: the current device's torch grid cap.  Writes
@@ -453,6 +453,45 @@ int fks_expand_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, con
                      void* workspace, size_t ws_bytes, void* stream);
 int fks_expand_launch_cuts(const fks_tensor* t, int32_t nt, int32_t k, int32_t shard, int32_t nshards, int64_t work,
                            int64_t max_grid, int64_t* cuts, int32_t cap, int32_t* ncuts);
+
+/* ---- seed-basis expansion written in place, CPU generator's stream (MT19937) ----
+ * fks_expand_mt_multi: fks_expand_multi on the CPU generator's stream, the other direction of
+ * fks_project_mt_multi.  outs, coefs and betas are fks_expand_multi's: a HOST array of nvec x nt
+ * fks_vec entries (each output FKS_F32, FKS_BF16 or FKS_F16 whatever the tensor's dtype, aligned
+ * to its element size only; entries of frozen and empty tensors are ignored and may be NULL),
+ * nvec x k doubles, nvec doubles or NULL.  The arithmetic is fks_expand_multi's word for word:
+ *   acc = +0.0f;  for s = 0 .. k-1 in order: acc = fmaf((float)coefs[m * k + s], z_s(i, e), acc);
+ *   out = cast(acc) if betas[m] == 0, else cast(fmaf((float)betas[m], widen(out), acc))
+ * over every non-frozen tensor i and element e that element shard `shard` of `nshards` owns --
+ * fks_project_mt's whole MT blocks (fks_shard_census) --, with z_s(i, e) the value fks_normal
+ * writes for seeds[s] on this stream in the tensor's dtype: the FKS_LIBM flavour where the list
+ * carries it, the ragged head and the 16-word tail recompute, the serial draws of numel < 16
+ * tensors with their cached second value.  With betas[m] == 0 the old output is never read; the
+ * rounding to the output's dtype happens once; zero coefficients are not skipped; k == 0 writes
+ * +0 where betas[m] == 0.  Frozen tensors advance the stream and are not written; elements
+ * outside the shard are not touched, and the union over the shards equals the one-shard call bit
+ * for bit.  An f32 output with beta 0 equals, bit for bit, the tensor's range of
+ * fks_delta_accumulate run on a zeroed buffer on this stream; row m equals the one-output call on
+ * output m (one output takes each pass of the generator; a larger nvec runs the passes again).
+ * k <= 19 is one pass of the 19-seed frame: the sums stay in registers and every output element
+ * is written once.  k > 19 runs passes of 19 seeds through an f32 staging area at the back of the
+ * workspace -- 4 bytes per element of the span of the concatenation the shard touches, one output
+ * at a time, never read before it is written; f32 stores lose nothing, so the chain is the one
+ * above.  Its size follows the shard, not the model: a caller bounds it by the shard count.
+ * Draws nothing from torch's generators; does not read or disturb the one-seed window cache, the
+ * z-index buffer or the attached reconstruct window cache; the tensors' data pointers are not
+ * read; the outputs' addresses key no cached plan (fks_project_mt_multi's geometry-only plan, one
+ * per tensor list and shard).  Workspace, in order: the per-call table (one 16-byte entry per
+ * output and per fast segment, run and single element, uploaded in stream order), the generator
+ * windows of one pass, the sink, the staging area: fks_expand_mt_multi_workspace_size for the
+ * same k, nvec, shard and nshards (8-byte aligned).  Errors are fks_expand_multi's, raised from
+ * the arguments alone before any allocation or launch: -FKS_EINVAL; a list that carries
+ * FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_expand_multi is the call for that stream).             */
+int fks_expand_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, int32_t shard,
+                                       int32_t nshards, size_t* bytes);
+int fks_expand_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                        const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                        void* workspace, size_t ws_bytes, void* stream);
 
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
