@@ -13,8 +13,13 @@ chunks of 2 and 3 MT blocks), 4,096 (fast), 3 frozen (serial draws, a cached sec
 behind), 1,000 (phase 8: a ragged head, 16 fresh tail words), 7 (its first element takes the cached
 value), 65,536 (a run whose 16-blocks straddle MT blocks), 0, 48; for f16 every run is irregular.
 K = 0 (a pass without seeds), 1 (a partial pass), 19 (a full pass), 20 (first + last through the
-staging area), 39 (first + middle + last).  fma32 runs on the device (test_gpu_expand_exact.py
-checks that it is the host's there)."""
+staging area), 39 (first + middle + last): there the last pass has 1 seed.  Four more K reach the
+pass shapes those leave out: 18 (a single pass one seed short of full), 37 (first + a last partial
+pass of 18 seeds), 38 (first + a last FULL pass: the instance that reads the staged carry and the
+old output and writes through beta and the cast with all 19 seeds unrolled) and 57 (first + middle
++ last full).  fma32 runs on the device (test_gpu_expand_exact.py checks that it is the host's
+there).  tests/test_gpu_expand_mt_layouts.py runs the same call over the lists of
+tests/mt_layouts.py."""
 import functools
 
 import pytest
@@ -30,8 +35,10 @@ pytestmark = pytest.mark.gpu
 
 _g = torch.Generator().manual_seed(20261021)
 SEEDS40 = SEEDS + torch.randint(0, 2**32, (20,), generator=_g).tolist()
+SEEDS57 = SEEDS40 + torch.randint(0, 2**32, (17,), generator=_g).tolist()  # the first 40 are SEEDS40
+KMAX = len(SEEDS57)
 ROWS = ["float32", "bfloat16", "float16"]  # output dtypes over the rows of a call
-KS = [0, 1, 19, 20, 39]
+KS = [0, 1, 19, 20, 39, 18, 37, 38, 57]  # (appended: a K's place sets its betas in test_chain_is_exact)
 KEPT = set(KS) | {7, 40}  # the K at which _sums keeps the chain
 
 
@@ -48,10 +55,10 @@ def _specs(dtype):
 
 @functools.lru_cache(maxsize=None)
 def _zs(dtype):
-    """the 40 seeds' draws over the concatenation as the reference draws them on the CPU (frozen
+    """the 57 seeds' draws over the concatenation as the reference draws them on the CPU (frozen
     tensors too), widened to f32, on the device; drawn once, shared, never written to"""
     out = []
-    for s in SEEDS40:
+    for s in SEEDS57:
         torch.manual_seed(s)
         z = [torch.normal(mean=0, std=1, size=(n,), dtype=DT[dtype]).float() for n in SIZES]
         out.append(torch.cat(z).to(_dev()))
@@ -65,7 +72,7 @@ def _sums(dtype, row, scale=1.0, special=()):
     zs = _zs(dtype)
     acc = torch.zeros_like(zs[0])
     out = {0: acc}
-    for k in range(40):
+    for k in range(KMAX):
         acc = fma32(torch.tensor(f32(coefs[k]), device=acc.device), zs[k], acc)
         if k + 1 in KEPT:
             out[k + 1] = acc
@@ -74,7 +81,7 @@ def _sums(dtype, row, scale=1.0, special=()):
 
 
 def _row(row, scale=1.0, special=()):
-    c = _coefs(40, row, scale)
+    c = _coefs(40, row, scale) + _coefs(KMAX - 40, 5000 + row, scale)  # (the first 40 as before the list grew)
     for at, v in special:
         c[at] = v
     return c
@@ -89,7 +96,7 @@ def _run(dtype, rows, row_names, betas=None, offset=0, k=39, nan_ok=False, check
     bs = [0.0] * M if betas is None else list(betas)
     made = [_buffers(L, row_names[m], bs[m], offset, dev, 700 + 100 * m) for m in range(M)]
     coefs = [_row(r, scale, special)[:k] for r in rows]
-    codec.expand_mt_multi(_specs(dtype), SEEDS40[:k], coefs, [v for _, v, _ in made], betas=betas, **kw)
+    codec.expand_mt_multi(_specs(dtype), SEEDS57[:k], coefs, [v for _, v, _ in made], betas=betas, **kw)
     torch.cuda.synchronize()
     if check:
         for m in range(M):
@@ -138,7 +145,7 @@ def test_f32_output_equals_delta_accumulate(dtype):
     zeroed buffer, bit for bit (for bf16 that path takes the slice kernel: other code)."""
     from fate_llm.algo.fedkseed import codec
     dev, L = _dev(), _list(dtype)
-    coefs = _row(87)
+    coefs = _row(87)[:40]
     outs = [torch.full((n,), float("nan"), dtype=torch.float32, device=dev) for n in SIZES]
     codec.expand_mt_multi(_specs(dtype), SEEDS40, [coefs], [outs])
     delta = torch.zeros(sum(SIZES), dtype=torch.float32, device=dev)
@@ -282,7 +289,7 @@ def test_torchs_generators_are_left_alone():
 
 
 # ---- 9. the other fp32 flavour
-@pytest.mark.parametrize("k", [19, 20])
+@pytest.mark.parametrize("k", [19, 20, 38])
 def test_other_fp32_flavour_equals_delta_accumulate(k):
     """The fp32 flavour that is not this process's (no torch draw of it exists here) against
     fks_delta_accumulate under the same setting, bit for bit; it differs from this process's."""
