@@ -13,6 +13,7 @@
 #include "fks_project_mt.h"
 #include "fks_expand.h"
 #include "fks_expand_mt.h"
+#include "fks_gram.h"
 
 namespace fks {
 
@@ -211,6 +212,10 @@ void phx_census(const PhxGeo& P, int nt, int shard, int nshards, int64_t* word_r
 // fks_expand_multi's launch cuts of the items [lo, hi): row boundaries lo = b[0] < ... < b[n] = hi, each
 // launch at most `work` seed-elements (4 per item x max(k, 1)) or a single row
 std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, int k, int64_t work);
+// fks_gram's passes, in launch order: rows [row0, row0 + nrows) against columns [col0, col0 + ncols),
+// at most kGramRows x kPhxSeeds; a symmetric call covers the pairs col >= row (and its diagonal tiles whole)
+struct GramPass { int32_t row0, nrows, col0, ncols; };
+std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric);
 
 // ================================================================== fks_cache.cpp
 // the current device and what the planning reads of it, read once per call
@@ -318,6 +323,10 @@ void device_selfcheck(int which, uint64_t* result, void* workspace, size_t ws_by
 size_t project_ws_bytes(const fks_tensor* t, int nt, int nvec, bool multi);
 void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, const fks_vec* vecs,
              int nvec, int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_gram: out[r][c] = <z_rows[r], z_cols[c]> (cols null: the symmetric Gram of rows, kc == kr)
+size_t gram_ws_bytes(const fks_tensor* t, int nt);
+void gram(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+          int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_project_mt: the same projection on the CPU generator's stream (the kModeDelta plan of vec)
 void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
                 double* dev_out, void* workspace, size_t ws_bytes, void* stream);

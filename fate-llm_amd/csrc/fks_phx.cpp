@@ -158,6 +158,22 @@ std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, in
   return b;
 }
 
+// Passes of fks_gram: tiles of at most kGramRows rows by at most kPhxSeeds columns, row tiles
+// outermost.  A rectangular call tiles its krows x kcols cells, every cell once.  A symmetric one
+// (kcols == krows) starts the columns of the row tile [r0, r0 + nr) at r0: its first pass is the
+// DIAGONAL tile, the only one that holds cells below the diagonal (c < r, both inside [r0, r0 + nr):
+// computed twice, with the same bits); every later pass of the row tile lies at c >= r0 + kPhxSeeds,
+// above every row.  So each pair c >= r is computed once and the reduce mirrors it.
+std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric) {
+  std::vector<GramPass> p;
+  for (int r0 = 0; r0 < krows; r0 += kGramRows) {
+    const int nr = std::min(kGramRows, krows - r0);
+    for (int c0 = symmetric ? r0 : 0; c0 < kcols; c0 += kPhxSeeds)
+      p.push_back(GramPass{r0, nr, c0, std::min(kPhxSeeds, kcols - c0)});
+  }
+  return p;
+}
+
 // element runs of whole Philox rows (phx_boundary)
 void phx_census(const PhxGeo& P, int nt, int shard, int nshards, int64_t* word_range, int64_t* written) {
   const int64_t lo = phx_boundary(P, shard, nshards), hi = phx_boundary(P, shard + 1, nshards);

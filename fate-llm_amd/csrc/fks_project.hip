@@ -31,11 +31,19 @@
 // [NV][kProjWaves][kPhxSeeds], partial[block][NV][kPhxSeeds]).  The walk, the seed loop and
 // the block's reduction are templates on NV and on the vector-fetch policy; fks_project_kernel
 // is their NV = 1, one-f32-buffer instance (156 VGPRs, no spill, as before the templates).
+//
+// fks_gram_kernel<NR> (include/fks.h fks_gram, fks_gram.h) is fks_project_multi_kernel<NR> with a
+// third fetch policy, ProjFetchDraw: the NR vectors of a group are not loaded but drawn, vector m
+// being the z of row seed m in the lane's tensor dtype.  Everything after the fetch -- the column
+// seeds' loop, the chains, the butterfly, the block's reduction -- is the projection's own code, so
+// <z_r, z_c> is, bit for bit, the projection of z_r on seed c (219 VGPRs, no scratch, two waves
+// per SIMD).  fks_gram_reduce_kernel is the reduce with the matrix's addressing and the mirror.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "fks_internal.h"
+#include "fks_gram.h"
 #include "fks_dev_zgen.h"
 
 namespace fks {
@@ -212,6 +220,61 @@ struct ProjFetchTable {
   }
 };
 
+// ProjFetchDraw: fks_gram's rows, drawn and not fetched.  Vector m of the group is the z of row
+// seed m in the lane's tensor dtype -- the values fks_normal writes, which are the values
+// proj_load_any reads from a buffer torch.normal filled --, in proj_load's places: v[m][i][q] =
+// z(element idx0 + q + S (4 j + i)), +0 for an element past the tensor's end.  The row loop is
+// not unrolled (one copy of the generator per item; the row's 32 values reach their registers
+// through selects on the wave-uniform m); rows past the pass's count are +0 and never reduced.
+// philox_round1 is written inside the row loop and not into an array above it: ctr and idx0 are
+// invariant there, so the compiler hoists what it has registers for, and an explicit r1[8] would
+// pin 32 VGPRs across the draw at 219 of 256 (the rows are 4 draws against a pass's 32 columns).
+template <int N>
+struct ProjFetchDraw {
+  static constexpr int NV = N;
+  const GramArgs& a;
+  __device__ __forceinline__ void load(const PhxTensor& T, int, uint32_t idx0, uint64_t j,
+                                       float v[N][4][kProjVec]) const {
+    const int64_t S = (int64_t)T.stride;
+    const int64_t e0 = (int64_t)idx0 + S * (int64_t)(4 * j);
+    const uint64_t ctr = T.off4 + j;
+    int room[4];  // run i holds elements q < room[i] of the tensor
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      room[i] = (int)std::min<int64_t>(std::max<int64_t>(T.numel - (e0 + S * i), 0), kProjVec);
+#pragma unroll
+    for (int m = 0; m < N; m++)
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int q = 0; q < kProjVec; q++) v[m][i][q] = 0.0f;
+#pragma unroll 1
+    for (int m = 0; m < a.nrows; m++) {
+      const uint64_t seed = a.rseeds[m];  // wave-uniform: a scalar load
+#pragma unroll
+      for (int q = 0; q < kProjVec; q++) {
+        const uint4 w = philox4x32_10(philox_round1(ctr, idx0 + (uint32_t)q), seed);
+        f32x2_t zA, zB;
+        if (T.dtype == FKS_BF16) {
+          phx_z_bf16(w, zA, zB);
+        } else {
+          phx_box_muller2(w, zA, zB);
+          if (T.dtype != FKS_F32) {
+            zA = (f32x2_t){phx_cast<FKS_F16>(zA.x), phx_cast<FKS_F16>(zA.y)};
+            zB = (f32x2_t){phx_cast<FKS_F16>(zB.x), phx_cast<FKS_F16>(zB.y)};
+          }
+        }
+        const float z[4] = {zA.x, zA.y, zB.x, zB.y};
+#pragma unroll
+        for (int mm = 0; mm < N; mm++)
+#pragma unroll
+          for (int i = 0; i < 4; i++) v[mm][i][q] = mm == m ? (q < room[i] ? z[i] : 0.0f) : v[mm][i][q];
+        __builtin_amdgcn_sched_barrier(0);  // one item's generator at a time
+      }
+    }
+  }
+};
+
 // Every seed of the pass over the wave's groups whose tensors draw dtype DT (`mine`: this
 // lane has such a group): the whole wave runs this, lanes that are not `mine` enter +0.
 // The z of a seed are drawn once; each of the NV vectors runs its own chain, q then i.
@@ -367,6 +430,29 @@ __global__ __launch_bounds__(kProjThreads, NV == 1 ? 1 : FKS_PROJ_MULTI_MIN_WAVE
   proj_block<(NV >= FKS_PROJ_MULTI_CVT_FROM)>(a, ProjFetchTable<NV>{a.vt, a.nt});
 }
 
+// fks_gram's pass: fks_project_multi_kernel<NR> with the vectors drawn (ProjFetchDraw), so row m
+// of the pass equals, bit for bit, fks_project_multi on a vector that holds row seed m's draw
+template <int NR>
+__global__ __launch_bounds__(kProjThreads, FKS_PROJ_MULTI_MIN_WAVES) void fks_gram_kernel(GramArgs a) {
+  proj_block<true>(a, ProjFetchDraw<NR>{a});
+}
+
+// fks_project_reduce_kernel's sum (the same lanes, blocks and butterfly) for one (column, row) of
+// a Gram pass, written to its element of the matrix and, for a symmetric call, to the transposed
+// one: <z_r, z_c> and <z_c, z_r> are the same products in the same order, so an element two
+// passes (or two blocks of a diagonal pass) write receives the same bits from both
+__global__ __launch_bounds__(64) void fks_gram_reduce_kernel(const double* partial, int nblocks, double* out,
+                                                             int64_t ld, int row0, int col0, int mirror) {
+  const int k = (int)blockIdx.x, m = (int)blockIdx.y;
+  double s = 0.0;
+  for (int b = (int)threadIdx.x; b < nblocks; b += 64) s += partial[((size_t)b * kGramRows + m) * kPhxSeeds + k];
+  s = wave_sum(s);
+  if (threadIdx.x == 0) {
+    out[(int64_t)(row0 + m) * ld + col0 + k] = s;
+    if (mirror) out[(int64_t)(col0 + k) * ld + row0 + m] = s;
+  }
+}
+
 // one wave per (seed, vector): lane l adds the partials of blocks l, l + 64, ... in order,
 // then the lanes' sums meet in the butterfly
 __global__ __launch_bounds__(64) void fks_project_reduce_kernel(const double* partial, int nblocks, double* out,
@@ -420,6 +506,29 @@ int launch_project_multi(const ProjectMultiArgs& a, void* stream) {
     case 3: project_multi_launch<3>(a, grid, lds, (hipStream_t)stream); break;
     default: project_multi_launch<4>(a, grid, lds, (hipStream_t)stream); break;
   }
+  return (int)hipGetLastError();
+}
+
+int launch_gram(const GramArgs& a, void* stream) {
+  const int64_t items = a.item_hi - a.item_lo;
+  if (a.nseeds < 1 || a.nseeds > kPhxSeeds || a.nrows < 1 || a.nrows > kGramRows || a.nt < 1 || items <= 0 ||
+      !a.partial)
+    return -FKS_EINVAL;
+  if (a.item_lo % kProjVec != 0 || items % kProjVec != 0) return -FKS_EINVAL;
+  const size_t lds =
+      (size_t)kProjAccBytes * (size_t)kGramRows + (a.nt <= kProjLdsTensors ? sizeof(PhxTensor) * (size_t)a.nt : 0);
+  hipLaunchKernelGGL(fks_gram_kernel<kGramRows>, dim3((unsigned)project_grid(items)), dim3(kProjThreads), lds,
+                     (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int launch_gram_reduce(const double* partial, int nblocks, int nrows, int ncols, double* out, int64_t ld, int row0,
+                       int col0, bool mirror, void* stream) {
+  if (ncols < 1 || ncols > kPhxSeeds || nrows < 1 || nrows > kGramRows || nblocks < 1 || row0 < 0 || col0 < 0 ||
+      (int64_t)col0 + ncols > ld || (mirror && (int64_t)row0 + nrows > ld))  // mirror: a square matrix of side ld
+    return -FKS_EINVAL;
+  hipLaunchKernelGGL(fks_gram_reduce_kernel, dim3((unsigned)ncols, (unsigned)nrows), dim3(64), 0, (hipStream_t)stream,
+                     partial, nblocks, out, ld, row0, col0, mirror ? 1 : 0);
   return (int)hipGetLastError();
 }
 

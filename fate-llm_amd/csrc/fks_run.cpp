@@ -537,6 +537,66 @@ void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fl
   }
 }
 
+// ---- seed-basis Gram matrix (torch_rocm stream) ----
+// fks_gram's workspace: the block partials of ONE pass, kGramRows x kPhxSeeds doubles per workgroup
+// of a launch over `items` work items (1 KiB x project_grid(items)); the passes follow each other
+// on the stream and share them.  Nothing depends on the seed counts or has the model's size.
+static size_t gram_need(int64_t items) {
+  return std::max<size_t>(sizeof(double) * (size_t)kGramRows * (size_t)kPhxSeeds * (size_t)project_grid(items), 256);
+}
+
+size_t gram_ws_bytes(const fks_tensor* t, int nt) {
+  return gram_need(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).items);
+}
+
+void gram(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+          int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  // the geometry on the host first: the workspace is checked before anything is allocated or launched
+  // (device_caps() reads the device's properties only and falls back to an MI355X's without a
+  // device, so the check below is made from the arguments alone, as tests/test_gram_host.py runs it)
+  const DevCaps dc = device_caps();
+  PhxGeo geo;
+  int64_t lo = 0, hi = 0;
+  if (nt > 0) {
+    geo = phx_geometry(t, nt, nullptr, 0, dc.max_grid);
+    lo = phx_boundary(geo, shard, nshards);
+    hi = phx_boundary(geo, shard + 1, nshards);
+  }
+  if (lo >= hi) {  // nothing in this shard: every inner product is +0
+    check_hip(hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)kr * (size_t)kc, (hipStream_t)stream),
+              "hipMemsetAsync");
+    return;
+  }
+  const size_t need = gram_need(hi - lo);
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < need)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(need) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = get_phx_plan(t, nt, nullptr, 0, dc);
+  if (P->nt != geo.nt) throw Error(-FKS_EINVAL, "torch_rocm plan does not match the call's geometry");
+  const int grid = project_grid(hi - lo);
+  GramArgs a{};
+  a.t = static_cast<const PhxTensor*>(P->dev);
+  a.nt = P->nt;
+  a.partial = static_cast<double*>(workspace);
+  a.item_lo = lo;
+  a.item_hi = hi;
+  for (const GramPass& p : gram_passes(kr, kc, symmetric)) {
+    for (int m = 0; m < kGramRows; m++) a.rseeds[m] = m < p.nrows ? rows[p.row0 + m] : 0;
+    for (int j = 0; j < p.ncols; j++) a.seeds[j] = cols[p.col0 + j];
+    a.nrows = p.nrows;
+    a.nseeds = p.ncols;
+    check_launch(timed(0, stream, [&] { return launch_gram(a, stream); }), "fks_gram_kernel", "bad arguments");
+    check_launch(launch_gram_reduce(a.partial, grid, p.nrows, p.ncols, dev_out, kc, p.row0, p.col0, symmetric, stream),
+                 "fks_gram_reduce_kernel", "bad arguments");
+  }
+}
+
 // ---- seed-basis expansion (torch_rocm stream) ----
 // fks_expand_multi's workspace, one per-call table uploaded in stream order: the outputs' pieces
 // ([nvec][entries] ProjVecEntry, a tensor past 2^31 bytes has several entries), the seeds ([k] u64),

@@ -814,6 +814,57 @@ def _project_in_place(specs, seeds, vectors, mode, shard, nshards) -> torch.Tens
     return out
 
 
+# row seeds that share one pass of the generator in gram (csrc/fks_gram.h kGramRows), against up to
+# 32 column seeds; larger calls run in tiles, with the same bits (tests/test_gram_host.py holds
+# the number against what fks_gram_passes reports)
+GRAM_PASS_ROWS = 4
+
+
+def gram(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, stream_mode=None,
+         shard: int = 0, nshards: int = 1) -> torch.Tensor:
+    """Seed-basis Gram matrix (include/fks.h fks_gram): out[r, c] = <z_r, z_c> over the non-frozen
+    specs' elements that element shard ``shard`` of ``nshards`` owns (``project``'s shards; the
+    shards' results add up to the whole call's), z_s the torch_rocm stream's draw for seed s in
+    each spec's dtype.  With ``col_seeds`` None it is the symmetric Gram matrix Z^T Z of
+    ``seeds``, float64[K, K], of which only the upper triangle is computed and the rest mirrored;
+    otherwise float64[Kr, Kc] for the rows ``seeds`` and the columns ``col_seeds``.  Duplicate
+    seeds are allowed.  The z are drawn inside the kernel: nothing of the model's size is read,
+    written or allocated (the workspace is a few MiB, whatever K).  out[r, c] equals, bit for bit,
+    ``project_multi(specs, [col seed c], [torch's draw for row seed r])``: it depends on the
+    device, the spec list, the shard and its two seeds only -- not on the other seeds, their order
+    or the tiling --, and the matrix is exactly symmetric.  Returns the matrix on the specs'
+    device, queued on the current stream; the argument checks and the plan (the spec list's
+    geometry-only one) are ``project_multi``'s, and the specs' data is not read.  No specs at all:
+    zeros on the CPU.  Draws nothing from torch's generators.  torch_rocm stream only: a call
+    that resolves to torch_cpu raises NotImplementedError."""
+    specs = list(specs)
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: gram() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws)")
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    rows = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    cols = None if col_seeds is None else np.ascontiguousarray([_seed_u64(x) for x in col_seeds], dtype=np.uint64)
+    shape = (len(rows), len(rows) if cols is None else len(cols))
+    if b.device is None:  # no spec at all
+        return torch.zeros(shape, dtype=torch.float64)
+    out = torch.empty(shape, dtype=torch.float64, device=b.device)
+    if not out.numel():
+        return out
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_gram_workspace_size(ctypes.addressof(b.arr), b.n, shape[0], shape[1], ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_gram(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
+                           None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1], int(shard),
+                           int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    return out  # ws goes back to torch's allocator in stream order
+
+
 # outputs that share one pass of the generator in expand_multi (csrc/fks_expand.h kExpMaxVec;
 # more run in batches, with the same bits)
 EXPAND_PASS_OUTPUTS = 4

@@ -277,7 +277,7 @@ int fks_delta_apply(const fks_tensor* t, int32_t nt, const float* delta, const d
  * seeds, Z^T v.  With v = grad f these are the exact directional derivatives of all K
  * candidates from one backward pass -- the wire's own K scalars (fedkseed.py:136-141 applies
  * them) --; with v a dense delta, Z^T v / N are its least-squares scalars in the candidates'
- * span for K << N (the Gram matrix Z^T Z is N I in expectation only); and
+ * span for K << N (the Gram matrix Z^T Z is N I in expectation only; fks_gram computes it); and
  * |Z^T g|^2 / (N |g|^2) is the share of a gradient the K-seed subspace captures.
  *
  * fks_project: dev_out[s] = sum over the non-frozen tensors i and the elements e that element
@@ -339,6 +339,56 @@ typedef struct fks_vec {
 int fks_project_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
 int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs, int32_t nvec,
                       int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- seed-basis Gram matrix: G[r][c] = <z_r, z_c> (FKS_STREAM_ROCM only) ----
+ * The third operator of the seed basis, Z^T Z, beside Z c (fks_expand_multi) and Z^T v
+ * (fks_project): with it the least-squares scalars (Z^T Z)^-1 Z^T delta, the share of a gradient
+ * the seed span captures and the norms |z_k|^2 are exact, where Z^T v / N errs by sqrt(K / N).
+ * fks_gram: dev_out[r * kc + c] = sum over the non-frozen tensors i and the elements e that
+ * element shard `shard` of `nshards` owns of (double)z_{row_seeds[r]}(i, e) *
+ * (double)z_{col_seeds[c]}(i, e), r < krows, c < kc, with z_s(i, e) the value fks_normal writes
+ * for seed s in t[i].dtype.  col_seeds == NULL is the symmetric Gram matrix of row_seeds: kcols
+ * must then be 0 or krows, kc = krows, only the pairs c >= r are computed (and the few below the
+ * diagonal that share a diagonal tile) and every element is also written to its transposed
+ * place (the output of the symmetric form is square, krows x krows, its row stride krows).
+ * Otherwise kc = kcols and the krows x kcols cells are computed as they stand.
+ * Duplicate seeds are allowed.  The z are drawn inside the kernel: no vector is read, nothing
+ * of the model's size is written or allocated.
+ * Contract: dev_out[r * kc + c] equals, bit for bit, fks_project_multi's result for the seed
+ * col_seeds[c] on the ONE vector whose entry for tensor i holds z_{row_seeds[r]}(i, .) in
+ * t[i].dtype (what fks_normal, or torch.normal after torch.manual_seed, writes there), over the
+ * same shard: the same grid, groups and fma chain (exact f64 products, one rounding per
+ * addition), wave butterfly, waves in wave order, blocks in block order; no floating-point
+ * atomic.  So an element depends on the device, the tensor list, the shard and its two seeds,
+ * and on nothing else -- not on the other seeds of the call, their order or their number, nor
+ * on how the call is tiled into passes (at most 4 row seeds by 32 column seeds each;
+ * fks_gram_passes) --, and since <z_r, z_c> and <z_c, z_r> are the same products in the same
+ * order the matrix is exactly symmetric, whichever form computes it.  The shards are
+ * fks_project's whole Philox rows (fks_shard_census); the shards' results add up to the whole
+ * call's.  Frozen tensors advance the Philox offset and contribute nothing.  dev_out (krows * kc
+ * doubles, row-major, device memory, 8-byte aligned) is OVERWRITTEN in stream order, every
+ * element of it, never accumulated into; an element written twice receives the same bits.  lr,
+ * wd and the other flags are ignored; the tensors' data pointers are not read.  Draws nothing
+ * from torch's generators.  krows == 0, kcols == 0 with column seeds given, nt == 0 and
+ * all-empty or all-frozen lists succeed; a shard with no element zeroes its output.
+ * Workspace: fks_gram_workspace_size (8-byte aligned): the block partials of one pass,
+ *   8 bytes x 4 rows x 32 columns x workgroups of the walk over the list's work items
+ * (at least 256 bytes; 16 workgroups per CU at most: 4 MiB on 256 CUs), whatever krows and kcols.
+ * Errors, raised from the arguments alone before any device work: krows or kcols < 0, a NULL
+ * row_seeds with krows > 0, kcols other than 0 or krows with a NULL col_seeds, a NULL or
+ * misaligned dev_out for a non-empty output, a bad shard, a NULL, misaligned or too small
+ * workspace: -FKS_EINVAL; tensors of the CPU generator's stream (no FKS_STREAM_ROCM, with or
+ * without FKS_LIBM): -FKS_ENOTSUP.
+ * fks_gram_passes (host arithmetic only; diagnostics, tests): the launches fks_gram makes for
+ * krows x kcols seeds, in order, as quadruples (row0, nrows, col0, ncols) of int32; symmetric
+ * != 0 is the col_seeds == NULL form (kcols 0 or krows).  A symmetric call starts the columns
+ * of a row tile at the tile's first row: that pass is the diagonal tile, the only one with cells
+ * below the diagonal.  Writes at most cap quadruples and sets *n to their number.          */
+int fks_gram_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
+int fks_gram(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows, const uint64_t* col_seeds,
+             int32_t kcols, int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes,
+             void* stream);
+int fks_gram_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
 
 /* ---- seed-basis projection on the CPU generator's stream (MT19937) ----
  * fks_project_mt: fks_project's contract on the other stream.  dev_out[s] = sum over the
