@@ -193,7 +193,8 @@ static void gram_check_stream(const fks_tensor* t, int nt) {
   if (nt == 0 || rocm_stream(t, nt)) return;
   throw Error(-FKS_ENOTSUP, std::string("fks_gram: the torch_cpu stream (the CPU generator's MT19937 stream") +
                                 (libm_flavour(t, nt) ? ", FKS_LIBM flavour" : "") +
-                                ") is not supported; the Gram matrix is built for FKS_STREAM_ROCM (torch_rocm) only");
+                                ") is not supported; the Gram matrix is built for FKS_STREAM_ROCM (torch_rocm) only "
+                                "here, fks_gram_mt is the call for this stream");
 }
 // the seed counts of a call: col_seeds NULL is the symmetric form, whose kcols is 0 or krows
 static void gram_check_counts(int32_t krows, int32_t kcols, bool symmetric) {
@@ -378,6 +379,54 @@ int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
     project_mt_multi_check_stream(t, nt);
     if (k == 0 || nvec == 0) return;
     project_mt_multi(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
+// ---- seed-basis Gram matrix (CPU generator's stream) ----
+static void gram_mt_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_gram_mt: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_gram is the call for that stream");
+}
+
+int fks_gram_mt_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || krows < 0 || kcols < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    gram_mt_check_stream(t, nt);
+    *bytes = gram_mt_ws(t, nt, 0, 1, device_cu_count()).total;
+  });
+}
+
+int fks_gram_mt(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows, const uint64_t* col_seeds,
+                int32_t kcols, int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes,
+                void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    check_shard(shard, nshards);
+    gram_check_counts(krows, kcols, col_seeds == nullptr);
+    if (krows > 0 && !row_seeds) throw Error(-FKS_EINVAL, "null row seed array");
+    const int32_t kc = col_seeds ? kcols : krows;
+    if (krows > 0 && kc > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned Gram output");
+    gram_mt_check_stream(t, nt);
+    if (krows == 0 || kc == 0) return;
+    gram_mt(t, nt, row_seeds, krows, col_seeds, kc, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
+int fks_gram_mt_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n) {
+  return guarded([&] {
+    if (cap < 0 || !n || (cap > 0 && !passes)) throw Error(-FKS_EINVAL, "bad arguments");
+    gram_check_counts(krows, kcols, symmetric != 0);
+    const std::vector<GramPass> p = gram_mt_passes(krows, symmetric ? krows : kcols, symmetric != 0);
+    *n = (int32_t)std::min<size_t>(p.size(), (size_t)INT32_MAX);
+    for (size_t i = 0; i < p.size() && i < (size_t)cap; i++) {
+      passes[4 * i + 0] = p[i].row0;
+      passes[4 * i + 1] = p[i].nrows;
+      passes[4 * i + 2] = p[i].col0;
+      passes[4 * i + 3] = p[i].ncols;
+    }
   });
 }
 

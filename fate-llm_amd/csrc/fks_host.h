@@ -14,6 +14,7 @@
 #include "fks_expand.h"
 #include "fks_expand_mt.h"
 #include "fks_gram.h"
+#include "fks_gram_mt.h"
 
 namespace fks {
 
@@ -138,6 +139,16 @@ struct ExpMtWs {
   size_t win_off = 0, sink_off = 0, stage_off = 0, stage_bytes = 0, total = 0;
 };
 ExpMtWs expand_mt_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
+// fks_gram_mt's, for one shard's plan (bounds; shard 0 of 1 bounds every shard): [row tile's and
+// column tile's windows at the regular chunk starts | the same at the irregular chunk starts |
+// partial rows of one pass].  The seed counts enter as min(k, tile) only.
+struct GramMtWs {
+  bool work = false;                   // the shard holds an element of a non-frozen tensor
+  int reg_chunks = 0, irr_chunks = 0;  // chunks of the plan's launches, at most
+  int rows = 0;                        // partial rows of one pass, at most
+  size_t irr_off = 0, partial_off = 0, total = 0;
+};
+GramMtWs gram_mt_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -216,6 +227,8 @@ std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, in
 // at most kGramRows x kPhxSeeds; a symmetric call covers the pairs col >= row (and its diagonal tiles whole)
 struct GramPass { int32_t row0, nrows, col0, ncols; };
 std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric);
+// fks_gram_mt's: the same order for its tile of kGramMtRows x kGramMtCols (fks_gram_mt.h)
+std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric);
 
 // ================================================================== fks_cache.cpp
 // the current device and what the planning reads of it, read once per call
@@ -333,6 +346,9 @@ void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const
 // fks_project_mt_multi: nvec vectors read in place (vecs[nvec][nt]) over the geometry-only plan
 void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
                       int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_gram_mt: fks_gram on the CPU generator's stream, over the geometry-only plan
+void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+             int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_expand_multi: nvec outputs written in place (outs[nvec][nt]), coefs[nvec][k], betas[nvec] or null
 int64_t expand_launch_work();  // kExpLaunchWork, or FKS_EXPAND_WORK where it is set to a positive number
 size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec);

@@ -360,6 +360,31 @@ ExpMtWs expand_mt_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, in
   return w;
 }
 
+// fks_gram_mt's workspace: the windows of a row tile and of a column tile at the regular chunk
+// starts, the same at the irregular chunk starts (the row tile's stay while its column tiles
+// pass, so the two chunk tables cannot share one area as they do in fks_project_mt), then one
+// pass's partial rows [row][kGramRows][kPhxSeeds].  Sized for a full tile whatever the seed
+// counts: nothing depends on them, and nothing has the model's size.
+GramMtWs gram_mt_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus) {
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  GramMtWs w;
+  int ndt = 0;
+  for (int d = 0; d < 3; d++) ndt += L.segs[d].empty() ? 0 : 1;
+  if (ndt) w.reg_chunks = plan_nchunks(std::max<int64_t>(1, br.hi - br.lo), false, cus);
+  int64_t covered = 0;  // owner blocks of the irregular work
+  for (auto& x : irregular_owner_intervals(L)) covered += x.second - x.first;
+  if (covered) w.irr_chunks = plan_nchunks(covered, false, cus);
+  w.work = ndt > 0 || w.irr_chunks > 0;
+  w.rows = ndt * w.reg_chunks + w.irr_chunks;
+  const size_t win = sizeof(uint32_t) * kMtN * (size_t)(kGramMtRows + kGramMtCols);
+  w.irr_off = align_up(win * (size_t)std::max(w.reg_chunks, 1), 256);
+  w.partial_off = w.irr_off + align_up(win * (size_t)std::max(w.irr_chunks, 1), 256);
+  w.total = w.partial_off + sizeof(double) * (size_t)kGramRows * (size_t)kPhxSeeds * (size_t)std::max(w.rows, 1);
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

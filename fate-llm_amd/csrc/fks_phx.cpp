@@ -164,14 +164,24 @@ std::vector<int64_t> phx_expand_cuts(const PhxGeo& P, int64_t lo, int64_t hi, in
 // DIAGONAL tile, the only one that holds cells below the diagonal (c < r, both inside [r0, r0 + nr):
 // computed twice, with the same bits); every later pass of the row tile lies at c >= r0 + kPhxSeeds,
 // above every row.  So each pair c >= r is computed once and the reduce mirrors it.
-std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric) {
+static std::vector<GramPass> gram_tile_passes(int krows, int kcols, bool symmetric, int tile_rows, int tile_cols) {
   std::vector<GramPass> p;
-  for (int r0 = 0; r0 < krows; r0 += kGramRows) {
-    const int nr = std::min(kGramRows, krows - r0);
-    for (int c0 = symmetric ? r0 : 0; c0 < kcols; c0 += kPhxSeeds)
-      p.push_back(GramPass{r0, nr, c0, std::min(kPhxSeeds, kcols - c0)});
+  for (int r0 = 0; r0 < krows; r0 += tile_rows) {
+    const int nr = std::min(tile_rows, krows - r0);
+    for (int c0 = symmetric ? r0 : 0; c0 < kcols; c0 += tile_cols)
+      p.push_back(GramPass{r0, nr, c0, std::min(tile_cols, kcols - c0)});
   }
   return p;
+}
+
+std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric) {
+  return gram_tile_passes(krows, kcols, symmetric, kGramRows, kPhxSeeds);
+}
+
+// fks_gram_mt's passes: the same tiling by kGramMtRows x kGramMtCols (columns >= rows, so the
+// diagonal tile still holds every cell below the diagonal of its row tile)
+std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric) {
+  return gram_tile_passes(krows, kcols, symmetric, kGramMtRows, kGramMtCols);
 }
 
 // element runs of whole Philox rows (phx_boundary)

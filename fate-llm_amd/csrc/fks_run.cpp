@@ -892,6 +892,110 @@ void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k,
   }
 }
 
+// ---- seed-basis Gram matrix (CPU generator's stream) ----
+// gram's passes over project_mt_multi's geometry-only plan.  The windows of a pass lie in the
+// workspace as the kernels read them, the row tile's first and the column tile's behind them,
+// once at the regular and once at the irregular chunk starts: the row tile's are jumped when the
+// row tile begins and stay while its column tiles pass, the column tile's are jumped per pass.
+// Then the launches of a project_mt pass -- one per dtype with fast segments, the irregular one
+// -- and gram's reduce over the rows they left.  No per-call table: nothing is read.
+void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+             int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  // the layout on the host first: the workspace is checked before anything is allocated or launched
+  const DevCaps dc = device_caps();
+  GramMtWs W;
+  if (nt > 0) W = gram_mt_ws(t, nt, shard, nshards, dc.cus);
+  if (!W.work) {  // nothing in this shard: every inner product is +0
+    check_hip(hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)kr * (size_t)kc, (hipStream_t)stream),
+              "hipMemsetAsync");
+    return;
+  }
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < W.total)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(W.total) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  int prows = C->have_irr ? C->Z.irr_chunks : 0;
+  for (int d = 0; d < 3; d++) prows += C->nsegs[d] ? C->Z.reg_chunks : 0;
+  if (prows < 1 || prows > W.rows || (C->have_reg && C->Z.reg_chunks > W.reg_chunks) ||
+      (C->have_irr && C->Z.irr_chunks > W.irr_chunks))
+    throw Error(-FKS_EINVAL, "the plan does not match the call's workspace layout");
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint32_t* const reg_states = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* const irr_states = reinterpret_cast<uint32_t*>(ws + W.irr_off);
+  double* const partial = reinterpret_cast<double*>(ws + W.partial_off);
+  const size_t reg_win = (size_t)kMtN * (size_t)C->Z.reg_chunks, irr_win = (size_t)kMtN * (size_t)C->Z.irr_chunks;
+  // the jump of n seeds to the regular (irregular) chunk starts, their windows from window `first` on
+  auto jump_reg = [&](const uint64_t* seeds, int n, int first) {
+    JumpArgs ja = jump_args(seeds, n, hdr, C->H.off_polys, C->H.off_cb, reg_states + (size_t)first * reg_win,
+                            C->Z.reg_chunks);
+    ja.chunks_per_wg = jump_chunks_per_wg(n, C->Z.reg_chunks, dc.cus);
+    check_launch(timed(1, stream, [&] { return launch_jump(ja, n, stream); }), "fks_jump_kernel");
+  };
+  auto jump_irr = [&](const uint64_t* seeds, int n, int first) {
+    JumpArgs ja = jump_args(seeds, n, hdr, C->H.off_ipolys, C->H.off_ilo, irr_states + (size_t)first * irr_win,
+                            C->Z.irr_chunks);
+    ja.chunks_per_wg = std::max(1, std::min(32, C->Z.irr_chunks));
+    check_launch(timed(1, stream, [&] { return launch_jump(ja, n, stream); }), "fks_jump_kernel");
+  };
+  int tile_row0 = -1;
+  for (const GramPass& p : gram_mt_passes(kr, kc, symmetric)) {
+    if (p.row0 != tile_row0) {  // a new row tile: its windows, once
+      tile_row0 = p.row0;
+      if (C->have_reg) jump_reg(rows + p.row0, p.nrows, 0);
+      if (C->have_irr) jump_irr(rows + p.row0, p.nrows, 0);
+    }
+    double* row = partial;
+    if (C->have_reg) {
+      jump_reg(cols + p.col0, p.ncols, p.nrows);
+      for (int d = 0; d < 3; d++) {
+        if (!C->nsegs[d]) continue;
+        GramMtArgs ga{};
+        ga.states = reg_states;
+        ga.segs = reinterpret_cast<const DevSeg*>(hdr + C->seg_off[d]);
+        ga.chunk_block = reinterpret_cast<const int64_t*>(hdr + C->H.off_cb);
+        ga.partial = row;
+        ga.nsegs = C->nsegs[d];
+        ga.nchunks = C->Z.reg_chunks;
+        ga.nrows = p.nrows;
+        ga.ncols = p.ncols;
+        const int dd = (d == FKS_F32 && libm) ? kDtF32Libm : d;
+        check_launch(timed(0, stream, [&] { return launch_gram_mt(dd, ga, stream); }), "fks_gram_mt_kernel",
+                     "bad arguments");
+        row += (size_t)kGramRows * (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+      }
+    }
+    if (C->have_irr) {
+      jump_irr(cols + p.col0, p.ncols, p.nrows);
+      GramMtIrrArgs ia{};
+      ia.states = irr_states;
+      ia.runs = reinterpret_cast<const DevRun*>(hdr + C->H.off_runs);
+      ia.tiny = reinterpret_cast<const DevTiny*>(hdr + C->H.off_tiny);
+      ia.chunk_lo = reinterpret_cast<const int64_t*>(hdr + C->H.off_ilo);
+      ia.chunk_hi = reinterpret_cast<const int64_t*>(hdr + C->H.off_ihi);
+      ia.partial = row;
+      ia.nruns = C->Z.nruns;
+      ia.ntiny = C->Z.ntiny;
+      ia.nchunks = C->Z.irr_chunks;
+      ia.nseeds = p.nrows + p.ncols;
+      ia.libm = libm ? 1 : 0;
+      ia.nrows = p.nrows;
+      ia.ncols = p.ncols;
+      check_launch(timed(0, stream, [&] { return launch_gram_mt_irr(ia, stream); }), "fks_gram_mt_irr_kernel",
+                   "bad arguments");
+    }
+    check_launch(launch_gram_reduce(partial, prows, p.nrows, p.ncols, dev_out, kc, p.row0, p.col0, symmetric, stream),
+                 "fks_gram_reduce_kernel", "bad arguments");
+  }
+}
+
 // ---- seed-basis expansion (CPU generator's stream) ----
 // project_mt_multi's frame run the other way: the geometry-only plan, the per-call table of the
 // outputs' pieces at the front of the workspace, then per output the passes of kMaxSeedsPerPass

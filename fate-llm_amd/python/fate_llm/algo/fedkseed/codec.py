@@ -836,13 +836,14 @@ def gram(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, strea
     device, queued on the current stream; the argument checks and the plan (the spec list's
     geometry-only one) are ``project_multi``'s, and the specs' data is not read.  No specs at all:
     zeros on the CPU.  Draws nothing from torch's generators.  torch_rocm stream only: a call
-    that resolves to torch_cpu raises NotImplementedError."""
+    that resolves to torch_cpu raises NotImplementedError (``gram_mt`` is that stream's call)."""
     specs = list(specs)
     device = specs[0].tensor.device if specs else torch.device("cpu")
     mode = resolve_stream_mode(device, stream_mode)
     if mode != "torch_rocm":
         raise NotImplementedError(f"FedKSeed codec: gram() is built for the torch_rocm stream only; this call "
-                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws)")
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), whose "
+                                  "call is gram_mt()")
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
@@ -862,6 +863,66 @@ def gram(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, strea
         N.check(L.fks_gram(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
                            None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1], int(shard),
                            int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value), _stream_handle(b.device)))
+    return out  # ws goes back to torch's allocator in stream order
+
+
+def _gram_mt_tile():
+    """(rows, columns) of gram_mt's pass (csrc/fks_gram_mt.h FKS_GMT_ROWS x FKS_GMT_COLS), read from the
+    library: the tallest and widest pass of a call larger than any tile (host arithmetic only)."""
+    L = N.load()
+    n = ctypes.c_int32(0)
+    N.check(L.fks_gram_mt_passes(4096, 4096, 0, None, 0, ctypes.byref(n)))
+    buf = (ctypes.c_int32 * (4 * n.value))()
+    N.check(L.fks_gram_mt_passes(4096, 4096, 0, ctypes.addressof(buf), n.value, ctypes.byref(n)))
+    return max(buf[1::4]), max(buf[3::4])
+
+
+# codec.GRAM_MT_PASS_ROWS / codec.GRAM_MT_PASS_COLS: the row and column seeds that share one pass
+# of the generator in gram_mt (larger calls run in tiles, with the same bits).  Read from the
+# library on first use, so that importing the codec does not load it.
+def __getattr__(name):
+    if name in ("GRAM_MT_PASS_ROWS", "GRAM_MT_PASS_COLS"):
+        rows, cols = _gram_mt_tile()
+        globals().update(GRAM_MT_PASS_ROWS=rows, GRAM_MT_PASS_COLS=cols)
+        return rows if name == "GRAM_MT_PASS_ROWS" else cols
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def gram_mt(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, shard: int = 0,
+            nshards: int = 1) -> torch.Tensor:
+    """``gram`` on the torch_cpu stream (include/fks.h fks_gram_mt): out[r, c] = <z_r, z_c> over the
+    non-frozen specs' elements that element shard ``shard`` of ``nshards`` owns (``project_mt``'s
+    shards), z_s the CPU generator's MT19937 draw for seed s in each spec's dtype -- fp32 in the
+    process's flavour (``cpu_fp32_flavour``), as ``project_mt``.  ``col_seeds`` None is the
+    symmetric Gram matrix of ``seeds``, float64[K, K], the upper triangle computed and mirrored;
+    otherwise float64[Kr, Kc].  Duplicate seeds are allowed.  Both sides are drawn inside the
+    kernels: nothing of the model's size is read, written or allocated.  out[r, c] equals, bit
+    for bit, ``project_mt_multi(specs, [col seed c], [torch's CPU draw for row seed r])``: it
+    depends on the device, the spec list, the shard and its two seeds only, and the matrix is
+    exactly symmetric.  It takes no ``stream_mode`` (the stream is always torch_cpu) and has no
+    CPU path.  Returns the matrix on the specs' device, queued on the current stream; the plan is
+    ``project_mt_multi``'s geometry-only one and the specs' data is not read.  No specs at all:
+    zeros on the CPU.  Draws nothing from torch's generators and leaves the codec's caches alone."""
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    b = _Batch(list(specs), "torch_cpu", stage=False)  # the specs' data is not read: no staging copies
+    rows = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    cols = None if col_seeds is None else np.ascontiguousarray([_seed_u64(x) for x in col_seeds], dtype=np.uint64)
+    shape = (len(rows), len(rows) if cols is None else len(cols))
+    if b.device is None:  # no spec at all
+        return torch.zeros(shape, dtype=torch.float64)
+    out = torch.empty(shape, dtype=torch.float64, device=b.device)
+    if not out.numel():
+        return out
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_gram_mt_workspace_size(ctypes.addressof(b.arr), b.n, shape[0], shape[1], ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_gram_mt(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
+                              None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1], int(shard),
+                              int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
+                              _stream_handle(b.device)))
     return out  # ws goes back to torch's allocator in stream order
 
 

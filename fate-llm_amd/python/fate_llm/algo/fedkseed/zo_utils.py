@@ -356,7 +356,7 @@ def seed_gram(param_groups: List[dict], seeds: Sequence[int], col_seeds=None, st
     nothing --, so G is the Gram matrix of exactly the vectors ``seed_projections_in_place``
     projects on, and its diagonal holds their exact squared norms |z_k|^2.  Nothing of the
     model's size is allocated.  Queued on the current stream; torch's generators are left alone.
-    torch_rocm stream only."""
+    torch_rocm stream only; ``seed_gram_on_stream`` takes either stream."""
     params = [p for g in param_groups for p in g["params"]]
     specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
     return codec.gram(specs, seeds, col_seeds, stream_mode=stream_mode)
@@ -378,6 +378,31 @@ def _solve_normal_equations(G, b):
     return np.linalg.solve(low.T, y).T
 
 
+def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_stream):
+    """fit_seed_scalars_exact (on_stream False: torch_rocm only) and
+    fit_seed_scalars_exact_on_stream (True: either stream): the duplicate-seed check, b = Z^T delta
+    read in place, G = Z^T Z on the same stream, the host solve.  SYNCHRONISES: G and b are
+    copied to the host."""
+    seen = set()
+    for s in seeds:
+        if int(s) in seen:
+            raise ValueError(f"{name}: seed {int(s)} is given twice; the scalars of a repeated seed "
+                             "are not unique")
+        seen.add(int(s))
+    specs, vector_lists, n_live = _projection_specs(param_groups, delta_vector_lists)
+    if not specs or n_live == 0:
+        raise ValueError(f"{name}: no parameter requires grad")
+    mode = codec.resolve_stream_mode(specs[0].tensor.device, stream_mode)
+    if mode != "torch_rocm" and not on_stream:  # before the projection, which has a torch_cpu form, runs for nothing
+        raise NotImplementedError(f"{name}: the Gram matrix is built for the torch_rocm stream only here; "
+                                  f"this call resolves to the {mode} stream (fit_seed_scalars_exact_on_stream takes "
+                                  "either stream)")
+    b = _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
+    G = codec.gram_mt(specs, seeds) if mode == "torch_cpu" else codec.gram(specs, seeds, stream_mode=stream_mode)
+    x = _solve_normal_equations(G.cpu().numpy(), b.cpu().numpy())
+    return torch.from_numpy(np.ascontiguousarray(x)).to(b.device)
+
+
 def fit_seed_scalars_exact(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
                            stream_mode=None) -> torch.Tensor:
     """The exact least-squares form of ``fit_seed_scalars_in_place``: the scalars
@@ -391,24 +416,34 @@ def fit_seed_scalars_exact(param_groups: List[dict], seeds: Sequence[int], delta
     in.  The call SYNCHRONISES: G and b are copied to the host.  Duplicate seeds raise
     ValueError (their columns of Z coincide and the scalars are not unique), and so does a G
     that is not positive definite: more seeds than elements that require grad.  torch_rocm
-    stream only, as ``seed_gram``."""
-    seen = set()
-    for s in seeds:
-        if int(s) in seen:
-            raise ValueError(f"fit_seed_scalars_exact: seed {int(s)} is given twice; the scalars of a repeated seed "
-                             "are not unique")
-        seen.add(int(s))
-    specs, vector_lists, n_live = _projection_specs(param_groups, delta_vector_lists)
-    if not specs or n_live == 0:
-        raise ValueError("fit_seed_scalars_exact: no parameter requires grad")
-    mode = codec.resolve_stream_mode(specs[0].tensor.device, stream_mode)
-    if mode != "torch_rocm":  # before the projection, which has a torch_cpu form, runs for nothing
-        raise NotImplementedError(f"fit_seed_scalars_exact: the Gram matrix is built for the torch_rocm stream only; "
-                                  f"this call resolves to the {mode} stream")
-    b = _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
-    G = seed_gram(param_groups, seeds, stream_mode=stream_mode)
-    x = _solve_normal_equations(G.cpu().numpy(), b.cpu().numpy())
-    return torch.from_numpy(np.ascontiguousarray(x)).to(b.device)
+    stream only, as ``seed_gram``; ``fit_seed_scalars_exact_on_stream`` takes either stream."""
+    return _fit_exact("fit_seed_scalars_exact", param_groups, seeds, delta_vector_lists, stream_mode, False)
+
+
+def seed_gram_on_stream(param_groups: List[dict], seeds: Sequence[int], col_seeds=None, stream_mode=None) -> torch.Tensor:
+    """``seed_gram`` on either stream: a call that resolves to torch_rocm takes codec.gram, one
+    that resolves to torch_cpu codec.gram_mt (the precedent is ``seed_expansion_on_stream_``).
+    Arguments and result are ``seed_gram``'s; on torch_rocm the bits are ``seed_gram``'s too.  On
+    torch_cpu G is the Gram matrix of the CPU generator's draws -- the stream of a federation
+    whose reference clients train on the CPU --: its diagonal holds the exact |z_k|^2, and with
+    ``seed_projections_in_place`` it gives the share of a gradient the seed span captures."""
+    params = [p for g in param_groups for p in g["params"]]
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    if codec.resolve_stream_mode(device, stream_mode) == "torch_cpu":
+        return codec.gram_mt(specs, seeds, col_seeds)
+    return codec.gram(specs, seeds, col_seeds, stream_mode=stream_mode)
+
+
+def fit_seed_scalars_exact_on_stream(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                                     stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars_exact`` on either stream: b through codec.project_multi and G through
+    codec.gram on torch_rocm (``fit_seed_scalars_exact``'s bits), through codec.project_mt_multi
+    and codec.gram_mt on torch_cpu -- so a dense delta enters a federation on the CPU generator's
+    stream without the sqrt(K / N) error of ``fit_seed_scalars_in_place``.  Arguments, result and
+    errors (a repeated seed, a Gram matrix that is not positive definite) are
+    ``fit_seed_scalars_exact``'s.  The call SYNCHRONISES: G and b are copied to the host."""
+    return _fit_exact("fit_seed_scalars_exact_on_stream", param_groups, seeds, delta_vector_lists, stream_mode, True)
 
 
 def _expansion_outputs(params, outputs, m=None):

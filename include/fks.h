@@ -378,7 +378,7 @@ int fks_project_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, in
  * row_seeds with krows > 0, kcols other than 0 or krows with a NULL col_seeds, a NULL or
  * misaligned dev_out for a non-empty output, a bad shard, a NULL, misaligned or too small
  * workspace: -FKS_EINVAL; tensors of the CPU generator's stream (no FKS_STREAM_ROCM, with or
- * without FKS_LIBM): -FKS_ENOTSUP.
+ * without FKS_LIBM): -FKS_ENOTSUP (fks_gram_mt is the call for that stream).
  * fks_gram_passes (host arithmetic only; diagnostics, tests): the launches fks_gram makes for
  * krows x kcols seeds, in order, as quadruples (row0, nrows, col0, ncols) of int32; symmetric
  * != 0 is the col_seeds == NULL form (kcols 0 or krows).  A symmetric call starts the columns
@@ -456,6 +456,49 @@ int fks_project_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t
 int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
                          int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
                          size_t ws_bytes, void* stream);
+
+/* ---- seed-basis Gram matrix on the CPU generator's stream (MT19937) ----
+ * fks_gram_mt: fks_gram's contract on fks_project_mt's stream.  dev_out[r * kc + c] = sum over
+ * the non-frozen tensors i and the elements e that element shard `shard` of `nshards` owns of
+ * (double)z_{row_seeds[r]}(i, e) * (double)z_{col_seeds[c]}(i, e), r < krows, c < kc, with
+ * z_s(i, e) the value fks_normal writes for seed s on the CPU generator's stream in t[i].dtype
+ * (the FKS_LIBM flavour where the list carries it; the ragged head and the 16-word tail
+ * recompute, the serial numel < 16 draws with their cached second value).  col_seeds == NULL is
+ * the symmetric form: kcols must be 0 or krows, kc = krows, only the pairs c >= r are computed
+ * (and those below the diagonal that share a diagonal tile) and every element is also written to
+ * its transposed place.  Otherwise kc = kcols and the krows x kcols cells are computed as they
+ * stand.  Duplicate seeds are allowed.  Both sides are drawn inside the kernels: no vector is
+ * read, nothing of the model's size is written or allocated.
+ * Contract: dev_out[r * kc + c] equals, bit for bit, fks_project_mt_multi's result for the seed
+ * col_seeds[c] on the ONE vector whose entry for tensor i holds z_{row_seeds[r]}(i, .) in
+ * t[i].dtype, over the same shard: the same plan chunks, fma chain (exact f64 products, one
+ * rounding per addition), wave butterfly, waves in wave order and rows in row order; no
+ * floating-point atomic.  So an element depends on the device, the tensor list, the shard and
+ * its two seeds, and on nothing else -- not on the other seeds of the call, their order or their
+ * number, nor on how the call is tiled into passes (at most 4 row seeds by 5 column seeds each;
+ * fks_gram_mt_passes) --, and the matrix is exactly symmetric, whichever form computes it.  The
+ * shards are fks_project_mt's whole MT blocks; the shards' results add up to the whole call's.
+ * Frozen tensors advance the stream and contribute nothing.  dev_out (krows * kc doubles,
+ * row-major, device memory, 8-byte aligned) is OVERWRITTEN in stream order, every element of it;
+ * an element written twice receives the same bits.  lr, wd and the other flags are ignored; the
+ * tensors' data pointers are not read.  Draws nothing from torch's generators; neither reads nor
+ * disturbs the one-seed window cache, the z-index buffer or the attached reconstruct window
+ * cache; uses fks_project_mt_multi's geometry-only plan (one cache entry per tensor list and
+ * shard).  krows == 0, kcols == 0 with column seeds given, nt == 0 and all-empty or all-frozen
+ * lists succeed; a shard with no element zeroes its output.
+ * Workspace: fks_gram_mt_workspace_size (8-byte aligned; a function of the list and the device's
+ * CU count, whatever krows and kcols): the generator windows of one row tile and one column tile
+ * at the plan's regular and irregular chunk starts (the row tile's are jumped once per row tile
+ * and kept while its column tiles pass), and one pass's partial rows.
+ * Errors, raised from the arguments alone before any allocation or launch: those of fks_gram:
+ * -FKS_EINVAL; a list that carries FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_gram is the call for that
+ * stream).
+ * fks_gram_mt_passes: fks_gram_passes for this call's tile (host arithmetic only).           */
+int fks_gram_mt_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
+int fks_gram_mt(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows, const uint64_t* col_seeds,
+                int32_t kcols, int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes,
+                void* stream);
+int fks_gram_mt_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
 
 /* ---- seed-basis expansion written in place (torch_rocm stream) ----
  * fks_expand_multi: the other direction of fks_project_multi, Z c instead of Z^T v: nvec dense
