@@ -245,6 +245,56 @@ int fks_gram_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* pa
   });
 }
 
+// ---- tiled seed-basis Gram matrix (torch_rocm stream) ----
+static void gram_tiled_check_stream(const fks_tensor* t, int nt) {
+  if (nt == 0 || rocm_stream(t, nt)) return;
+  throw Error(-FKS_ENOTSUP, std::string("fks_gram_tiled: the torch_cpu stream (the CPU generator's MT19937 stream") +
+                                (libm_flavour(t, nt) ? ", FKS_LIBM flavour" : "") +
+                                ") is not supported; the tiled Gram matrix is built for FKS_STREAM_ROCM (torch_rocm) "
+                                "only, fks_gram_mt is the call for this stream");
+}
+
+int fks_gram_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || krows < 0 || kcols < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    gram_tiled_check_stream(t, nt);
+    *bytes = gram_tiled_ws_bytes(t, nt);
+  });
+}
+
+int fks_gram_tiled(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows, const uint64_t* col_seeds,
+                   int32_t kcols, int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes,
+                   void* stream) {
+  return guarded([&] {
+    validate(t, nt);
+    check_shard(shard, nshards);
+    gram_check_counts(krows, kcols, col_seeds == nullptr);
+    if (krows > 0 && !row_seeds) throw Error(-FKS_EINVAL, "null row seed array");
+    const int32_t kc = col_seeds ? kcols : krows;
+    if (krows > 0 && kc > 0 && (!dev_out || ((uintptr_t)dev_out % 8) != 0))
+      throw Error(-FKS_EINVAL, "null or misaligned Gram output");
+    gram_tiled_check_stream(t, nt);
+    if (krows == 0 || kc == 0) return;
+    gram_tiled(t, nt, row_seeds, krows, col_seeds, kc, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
+int fks_gram_tiled_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n) {
+  return guarded([&] {
+    if (cap < 0 || !n || (cap > 0 && !passes)) throw Error(-FKS_EINVAL, "bad arguments");
+    gram_check_counts(krows, kcols, symmetric != 0);
+    const std::vector<GramPass> p = gram_tiled_passes(krows, symmetric ? krows : kcols, symmetric != 0);
+    *n = (int32_t)std::min<size_t>(p.size(), (size_t)INT32_MAX);
+    for (size_t i = 0; i < p.size() && i < (size_t)cap; i++) {
+      passes[4 * i + 0] = p[i].row0;
+      passes[4 * i + 1] = p[i].nrows;
+      passes[4 * i + 2] = p[i].col0;
+      passes[4 * i + 3] = p[i].ncols;
+    }
+  });
+}
+
 // ---- seed-basis expansion (torch_rocm stream) ----
 static void expand_check_stream(const fks_tensor* t, int nt) {
   if (nt == 0 || rocm_stream(t, nt)) return;

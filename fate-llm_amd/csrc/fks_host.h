@@ -15,6 +15,7 @@
 #include "fks_expand_mt.h"
 #include "fks_gram.h"
 #include "fks_gram_mt.h"
+#include "fks_gram_tiled.h"
 
 namespace fks {
 
@@ -229,6 +230,8 @@ struct GramPass { int32_t row0, nrows, col0, ncols; };
 std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric);
 // fks_gram_mt's: the same order for its tile of kGramMtRows x kGramMtCols (fks_gram_mt.h)
 std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric);
+// fks_gram_tiled's: the same order for its tile of kGtRows x kGtCols (fks_gram_tiled.h)
+std::vector<GramPass> gram_tiled_passes(int krows, int kcols, bool symmetric);
 
 // ================================================================== fks_cache.cpp
 // the current device and what the planning reads of it, read once per call
@@ -340,6 +343,10 @@ void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fl
 size_t gram_ws_bytes(const fks_tensor* t, int nt);
 void gram(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
           int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_gram_tiled: fks_gram's matrix in passes of kGtRows x kGtCols seeds on the f64 matrix unit
+size_t gram_tiled_ws_bytes(const fks_tensor* t, int nt);
+void gram_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_project_mt: the same projection on the CPU generator's stream (the kModeDelta plan of vec)
 void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
                 double* dev_out, void* workspace, size_t ws_bytes, void* stream);

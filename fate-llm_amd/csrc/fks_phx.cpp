@@ -184,6 +184,12 @@ std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric) {
   return gram_tile_passes(krows, kcols, symmetric, kGramMtRows, kGramMtCols);
 }
 
+// fks_gram_tiled's passes: the same tiling by its tile of kGtRows x kGtCols seeds (fks_gram_tiled.h;
+// columns >= rows)
+std::vector<GramPass> gram_tiled_passes(int krows, int kcols, bool symmetric) {
+  return gram_tile_passes(krows, kcols, symmetric, kGtRows, kGtCols);
+}
+
 // element runs of whole Philox rows (phx_boundary)
 void phx_census(const PhxGeo& P, int nt, int shard, int nshards, int64_t* word_range, int64_t* written) {
   const int64_t lo = phx_boundary(P, shard, nshards), hi = phx_boundary(P, shard + 1, nshards);

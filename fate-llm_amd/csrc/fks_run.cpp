@@ -597,6 +597,73 @@ void gram(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint6
   }
 }
 
+// ---- tiled seed-basis Gram matrix (torch_rocm stream, f64 matrix unit) ----
+// fks_gram_tiled's workspace: the block partials of ONE pass, kGtRows x kGtCols doubles per workgroup
+// of a launch over `items` work items; the passes follow each other on the stream and share them.
+// Nothing depends on the seed counts or has the model's size.
+static size_t gram_tiled_need(int64_t items) {
+  return std::max<size_t>(sizeof(double) * (size_t)kGtTile * (size_t)gram_tiled_grid(items), 256);
+}
+
+size_t gram_tiled_ws_bytes(const fks_tensor* t, int nt) {
+  return gram_tiled_need(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).items);
+}
+
+// gram()'s driver over the tile of fks_gram_tiled.h: geometry first, the workspace check before any
+// allocation, the geometry-only plan, then per pass the kernel and the reduce with the matrix's
+// addressing and the mirror.  Seeds past a pass's counts are padded with 0 (drawn only where their
+// 16-block is live, never written out).
+void gram_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  const DevCaps dc = device_caps();
+  PhxGeo geo;
+  int64_t lo = 0, hi = 0;
+  if (nt > 0) {
+    geo = phx_geometry(t, nt, nullptr, 0, dc.max_grid);
+    lo = phx_boundary(geo, shard, nshards);
+    hi = phx_boundary(geo, shard + 1, nshards);
+  }
+  if (lo >= hi) {  // nothing in this shard: every inner product is +0
+    check_hip(hipMemsetAsync(dev_out, 0, sizeof(double) * (size_t)kr * (size_t)kc, (hipStream_t)stream),
+              "hipMemsetAsync");
+    return;
+  }
+  const size_t need = gram_tiled_need(hi - lo);
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < need)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(need) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = get_phx_plan(t, nt, nullptr, 0, dc);
+  if (P->nt != geo.nt) throw Error(-FKS_EINVAL, "torch_rocm plan does not match the call's geometry");
+  const int grid = gram_tiled_grid(hi - lo);
+  GramTiledArgs a{};
+  a.t = static_cast<const PhxTensor*>(P->dev);
+  a.nt = P->nt;
+  a.partial = static_cast<double*>(workspace);
+  a.item_lo = lo;
+  a.item_hi = hi;
+  for (const GramPass& p : gram_tiled_passes(kr, kc, symmetric)) {
+    for (int m = 0; m < kGtRows; m++) a.rseeds[m] = m < p.nrows ? rows[p.row0 + m] : 0;
+    for (int j = 0; j < kGtCols; j++) a.cseeds[j] = j < p.ncols ? cols[p.col0 + j] : 0;
+    a.nrb = (p.nrows + kGtSeeds - 1) / kGtSeeds;
+    a.ncb = (p.ncols + kGtSeeds - 1) / kGtSeeds;
+    // a column block that holds its row block's seeds takes the row block's operand (the diagonal
+    // tile of a symmetric call; the same values either way)
+    const int shared = std::min(a.nrb, a.ncb) * kGtSeeds;
+    a.diag = std::equal(a.rseeds, a.rseeds + shared, a.cseeds) ? 1 : 0;
+    check_launch(timed(0, stream, [&] { return launch_gram_tiled(a, stream); }), "fks_gram_tiled_kernel",
+                 "bad arguments");
+    check_launch(launch_gram_tiled_reduce(a.partial, grid, p.nrows, p.ncols, dev_out, kc, p.row0, p.col0, symmetric,
+                                          stream),
+                 "fks_gram_tiled_reduce_kernel", "bad arguments");
+  }
+}
+
 // ---- seed-basis expansion (torch_rocm stream) ----
 // fks_expand_multi's workspace, one per-call table uploaded in stream order: the outputs' pieces
 // ([nvec][entries] ProjVecEntry, a tensor past 2^31 bytes has several entries), the seeds ([k] u64),

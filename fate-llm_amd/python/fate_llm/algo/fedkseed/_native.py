@@ -37,6 +37,7 @@ EXPORTED = (
     "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
     "fks_gram_workspace_size", "fks_gram", "fks_gram_passes",
     "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
+    "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes",
 )
 
 
@@ -142,6 +143,9 @@ def load():
         L.fks_gram_mt_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_gram_mt.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         L.fks_gram_mt_passes.argtypes = [c_i32, c_i32, c_i32, P, c_i32, ctypes.POINTER(c_i32)]
+        L.fks_gram_tiled_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_gram_tiled.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
+        L.fks_gram_tiled_passes.argtypes = [c_i32, c_i32, c_i32, P, c_i32, ctypes.POINTER(c_i32)]
         for name in ("fks_workspace_size", "fks_directional_step", "fks_perturb", "fks_normal",
                      "fks_host_jump_window", "fks_host_tables", "fks_directional_step_shard",
                      "fks_stream_length", "fks_profile_begin", "fks_profile_end", "fks_shard_census", "fks_perturb_step",
@@ -155,7 +159,8 @@ def load():
                      "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
                      "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
                      "fks_gram_workspace_size", "fks_gram", "fks_gram_passes",
-                     "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes"):
+                     "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
+                     "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes"):
             getattr(L, name).restype = ctypes.c_int
         if L.fks_abi_version() != ABI_VERSION:
             raise OSError(f"libfks.so ABI {L.fks_abi_version()} != {ABI_VERSION}")

@@ -866,6 +866,65 @@ def gram(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, strea
     return out  # ws goes back to torch's allocator in stream order
 
 
+def gram_tiled(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, stream_mode=None,
+               shard: int = 0, nshards: int = 1) -> torch.Tensor:
+    """``gram`` in tiles of 64 x 64 seeds on the f64 matrix unit (include/fks.h fks_gram_tiled): the
+    same matrix, out[r, c] = <z_r, z_c> over the non-frozen specs' elements that element shard
+    ``shard`` of ``nshards`` owns, for seed counts where ``gram``'s passes of 4 x 32 seeds are too
+    many (K = 4096: 2,080 passes against 66,048).  Arguments, shapes and checks are ``gram``'s:
+    ``col_seeds`` None is the symmetric matrix float64[K, K] (the tiles on and above the diagonal
+    computed, the rest mirrored), otherwise float64[Kr, Kc]; duplicate seeds are allowed; nothing
+    of the model's size is read, written or allocated (the workspace is 8 MiB on an MI355X, whatever
+    K).  Every product is exact and every addition f64, in the kernel's own fixed order -- NOT
+    ``gram``'s: the two agree to within 2 n 2^-52 sum|z_r z_c| over the n live elements, not bit
+    for bit, and this call has no bit-for-bit relation to ``project_multi``.  out[r, c] depends on
+    the device, the spec list, the shard and its two seeds only -- not on the other seeds, their
+    order or number, the place in a tile or the passes --, and the matrix is exactly symmetric.
+    Returns the matrix on the specs' device, queued on the current stream.  No specs at all: zeros
+    on the CPU.  Draws nothing from torch's generators.  torch_rocm stream only: a call that
+    resolves to torch_cpu raises NotImplementedError (``gram_mt`` is that stream's only form)."""
+    specs = list(specs)
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    mode = resolve_stream_mode(device, stream_mode)
+    if mode != "torch_rocm":
+        raise NotImplementedError(f"FedKSeed codec: gram_tiled() is built for the torch_rocm stream only; this call "
+                                  f"resolves to the {mode} stream (the CPU generator's MT19937 draws), whose "
+                                  "call is gram_mt()")
+    if nshards < 1 or not 0 <= shard < nshards:
+        raise ValueError(f"shard {shard} of {nshards}")
+    b = _Batch(specs, mode, stage=False)  # the specs' data is not read: no staging copies, stable plan key
+    rows = np.ascontiguousarray([_seed_u64(x) for x in seeds], dtype=np.uint64)
+    cols = None if col_seeds is None else np.ascontiguousarray([_seed_u64(x) for x in col_seeds], dtype=np.uint64)
+    shape = (len(rows), len(rows) if cols is None else len(cols))
+    if b.device is None:  # no spec at all
+        return torch.zeros(shape, dtype=torch.float64)
+    out = torch.empty(shape, dtype=torch.float64, device=b.device)
+    if not out.numel():
+        return out
+    L = N.load()
+    with torch.cuda.device(b.device):
+        nbytes = ctypes.c_size_t(0)
+        N.check(L.fks_gram_tiled_workspace_size(ctypes.addressof(b.arr), b.n, shape[0], shape[1],
+                                                ctypes.byref(nbytes)))
+        ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
+        N.check(L.fks_gram_tiled(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
+                                 None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1],
+                                 int(shard), int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
+                                 _stream_handle(b.device)))
+    return out  # ws goes back to torch's allocator in stream order
+
+
+def _gram_tiled_tile():
+    """(rows, columns) in seeds of gram_tiled's pass (csrc/fks_gram_tiled.h), read from the library:
+    the tallest and widest pass of a call larger than any tile (host arithmetic only)."""
+    L = N.load()
+    n = ctypes.c_int32(0)
+    N.check(L.fks_gram_tiled_passes(4096, 4096, 0, None, 0, ctypes.byref(n)))
+    buf = (ctypes.c_int32 * (4 * n.value))()
+    N.check(L.fks_gram_tiled_passes(4096, 4096, 0, ctypes.addressof(buf), n.value, ctypes.byref(n)))
+    return max(buf[1::4]), max(buf[3::4])
+
+
 def _gram_mt_tile():
     """(rows, columns) of gram_mt's pass (csrc/fks_gram_mt.h FKS_GMT_ROWS x FKS_GMT_COLS), read from the
     library: the tallest and widest pass of a call larger than any tile (host arithmetic only)."""

@@ -378,11 +378,12 @@ def _solve_normal_equations(G, b):
     return np.linalg.solve(low.T, y).T
 
 
-def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_stream):
-    """fit_seed_scalars_exact (on_stream False: torch_rocm only) and
-    fit_seed_scalars_exact_on_stream (True: either stream): the duplicate-seed check, b = Z^T delta
-    read in place, G = Z^T Z on the same stream, the host solve.  SYNCHRONISES: G and b are
-    copied to the host."""
+def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_stream, tiled=False):
+    """fit_seed_scalars_exact (on_stream False: torch_rocm only),
+    fit_seed_scalars_exact_on_stream (True: either stream) and fit_seed_scalars_exact_tiled
+    (tiled True: torch_rocm only, G through codec.gram_tiled): the duplicate-seed check,
+    b = Z^T delta read in place, G = Z^T Z on the same stream, the host solve.  SYNCHRONISES: G
+    and b are copied to the host."""
     seen = set()
     for s in seeds:
         if int(s) in seen:
@@ -398,7 +399,10 @@ def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_st
                                   f"this call resolves to the {mode} stream (fit_seed_scalars_exact_on_stream takes "
                                   "either stream)")
     b = _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
-    G = codec.gram_mt(specs, seeds) if mode == "torch_cpu" else codec.gram(specs, seeds, stream_mode=stream_mode)
+    if tiled:
+        G = codec.gram_tiled(specs, seeds, stream_mode=stream_mode)
+    else:
+        G = codec.gram_mt(specs, seeds) if mode == "torch_cpu" else codec.gram(specs, seeds, stream_mode=stream_mode)
     x = _solve_normal_equations(G.cpu().numpy(), b.cpu().numpy())
     return torch.from_numpy(np.ascontiguousarray(x)).to(b.device)
 
@@ -418,6 +422,30 @@ def fit_seed_scalars_exact(param_groups: List[dict], seeds: Sequence[int], delta
     that is not positive definite: more seeds than elements that require grad.  torch_rocm
     stream only, as ``seed_gram``; ``fit_seed_scalars_exact_on_stream`` takes either stream."""
     return _fit_exact("fit_seed_scalars_exact", param_groups, seeds, delta_vector_lists, stream_mode, False)
+
+
+def seed_gram_tiled(param_groups: List[dict], seeds: Sequence[int], col_seeds=None, stream_mode=None) -> torch.Tensor:
+    """``seed_gram`` through codec.gram_tiled: the same matrix, G[r, c] = <z_r, z_c> over the
+    parameters that require grad, in passes of 64 x 64 seeds on the f64 matrix unit -- the form for
+    seed counts in the hundreds and thousands, where ``seed_gram``'s passes of 4 x 32 seeds are too
+    many.  Arguments and meaning are ``seed_gram``'s; the products are exact and the sums f64 in
+    a fixed order of the tiled kernel's own, so G is exactly symmetric and reproducible but agrees
+    with ``seed_gram`` to within 2 n 2^-52 sum|z_r z_c| only, not bit for bit.  torch_rocm stream
+    only; ``seed_gram`` and ``seed_gram_on_stream`` keep their bits and their routing."""
+    params = [p for g in param_groups for p in g["params"]]
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    return codec.gram_tiled(specs, seeds, col_seeds, stream_mode=stream_mode)
+
+
+def fit_seed_scalars_exact_tiled(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                                 stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars_exact`` with G from ``seed_gram_tiled``: the least-squares scalars
+    (Z^T Z)^-1 Z^T delta, float64[M, K], where K is large enough that G is the cost of the fit.
+    b, the host solve, the errors (a repeated seed, a G that is not positive definite) and the
+    synchronisation are ``fit_seed_scalars_exact``'s; the scalars differ from its by the f64
+    summation order of G only.  torch_rocm stream only."""
+    return _fit_exact("fit_seed_scalars_exact_tiled", param_groups, seeds, delta_vector_lists, stream_mode, False,
+                      tiled=True)
 
 
 def seed_gram_on_stream(param_groups: List[dict], seeds: Sequence[int], col_seeds=None, stream_mode=None) -> torch.Tensor:

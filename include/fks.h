@@ -390,6 +390,61 @@ int fks_gram(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t
              void* stream);
 int fks_gram_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
 
+/* ---- tiled seed-basis Gram matrix on the f64 matrix unit (FKS_STREAM_ROCM only) ----
+ * fks_gram_tiled: fks_gram's matrix for seed counts where fks_gram's 4 x 32 passes are too many:
+ * a pass is a tile of 64 row seeds by 64 column seeds (4 x 4 blocks of 16; v_mfma_f64_16x16x4_f64
+ * forms the 256 seed pairs of a block pair from one draw per (seed, element)), so K = 4096 is
+ * 2,080 passes where fks_gram makes 66,048.  Arguments, output shape and everything below the
+ * contract are fks_gram's: dev_out[r * kc + c], r < krows, c < kc; col_seeds == NULL is the
+ * symmetric form (kcols 0 or krows, kc = krows, square output of row stride krows; the tile
+ * passes on and above the diagonal are computed and every element is also written to its
+ * transposed place), otherwise kc = kcols and the krows x kcols cells are computed as they
+ * stand.  Duplicate seeds are allowed.  The z are drawn inside the kernel: no vector is read,
+ * nothing of the model's size is written or allocated.
+ * Contract: dev_out[r * kc + c] is the sum over the non-frozen tensors i and the elements e that
+ * element shard `shard` of `nshards` owns of (double)z_{row_seeds[r]}(i, e) *
+ * (double)z_{col_seeds[c]}(i, e), with z_s(i, e) the value fks_normal writes for seed s in
+ * t[i].dtype.  Every product is exact in f64 (24 + 24 significand bits) and every addition is
+ * f64.  The ORDER of the additions is this kernel's own: the matrix unit's order over the four
+ * work items of one MFMA, the MFMAs of a wave in a fixed walk (chunks of 256 work items, chunk
+ * g + n x the grid's waves for wave g; in a chunk four items at a time, an item's four elements
+ * in turn), the four waves of a workgroup in wave order, the workgroups in a fixed order (16
+ * interleaved runs in block order, then the runs in order); no floating-point atomic.  It is
+ * NOT fks_gram's order: the two calls do not agree bit for bit, and fks_gram_tiled has no
+ * bit-for-bit relation to fks_project_multi.  Each is within n 2^-52 sum |z_r z_c| of the true
+ * sum over the n live elements of the shard, as any f64 order is, so the two agree to within
+ * 2 n 2^-52 sum |z_r z_c|.
+ * Reproducibility: an element depends on the device, the tensor list, the shard and its two
+ * seeds, and on nothing else -- not on the other seeds of the call, their order or their number,
+ * where in a tile the pair falls, nor how the call is cut into passes (fks_gram_tiled_passes):
+ * the grid and the walk are functions of the device and the shard's work items alone, and every
+ * accumulator of a tile sees the same sequence of operations.  Rows and columns that pad a pass
+ * to a multiple of 16 are drawn from seed 0 and never written out; 16-blocks past the pass's
+ * counts are not drawn at all.  <z_r, z_c> and <z_c, z_r> are the same products in the same
+ * order, so the matrix is exactly symmetric, whichever form computes it; a column block that
+ * holds the seeds of a row block (the diagonal tile) takes the row block's draw as its operand.
+ * The shards are fks_project's whole Philox rows (fks_shard_census); the shards' results add up
+ * to the whole call's.  Frozen tensors advance the Philox offset and contribute nothing.
+ * dev_out (krows * kc doubles, row-major, device memory, 8-byte aligned) is OVERWRITTEN in
+ * stream order, every element of it, never accumulated into; an element written twice receives
+ * the same bits.  lr, wd and the other flags are ignored; the tensors' data pointers are not
+ * read.  Draws nothing from torch's generators.  krows == 0, kcols == 0 with column seeds given,
+ * nt == 0 and all-empty or all-frozen lists succeed; a shard with no element zeroes its output
+ * and needs no workspace.
+ * Workspace: fks_gram_tiled_workspace_size (8-byte aligned): the workgroup partials of one pass,
+ *   8 bytes x 64 x 64 x min(ceil(ceil(items / 256) / 4), CUs)
+ * with `items` the list's work items (at least 256 bytes; 32 KiB per workgroup, one workgroup
+ * per CU -- the kernel's own residency -- at most: 8 MiB on 256 CUs), whatever krows and kcols.
+ * Errors, raised from the arguments alone before any device work: those of fks_gram --
+ * -FKS_EINVAL --; tensors of the CPU generator's stream (no FKS_STREAM_ROCM, with or without
+ * FKS_LIBM): -FKS_ENOTSUP (fks_gram_mt is the only form for that stream).
+ * fks_gram_tiled_passes: fks_gram_passes for this call's tile (host arithmetic only).       */
+int fks_gram_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
+int fks_gram_tiled(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows,
+                   const uint64_t* col_seeds, int32_t kcols, int32_t shard, int32_t nshards, double* dev_out,
+                   void* workspace, size_t ws_bytes, void* stream);
+int fks_gram_tiled_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
+
 /* ---- seed-basis projection on the CPU generator's stream (MT19937) ----
  * fks_project_mt: fks_project's contract on the other stream.  dev_out[s] = sum over the
  * non-frozen tensors i and the elements e that element shard `shard` of `nshards` owns of
