@@ -1,5 +1,5 @@
 // fks_capi.cpp -- the C ABI of libfks.so (include/fks.h): argument checks and one call each into
-// fks_layout / fks_phx / fks_cache / fks_run.cpp.  Exceptions never cross it: guarded() returns codes.
+// fks_layout / fks_phx / fks_cache / fks_run / fks_run_basis.cpp.  Exceptions never cross it: guarded() returns codes.
 // Reference routines replaced (include/fks.h lists them): zo_utils.directional_derivative_step
 // (zo_utils.py:23-54), ZerothOrderOptimizer.random_perturb_parameters (optimizer.py:152-173),
 // and the per-seed reconstruct loop of ClientTrainer.train_once (fedkseed.py:136-141).

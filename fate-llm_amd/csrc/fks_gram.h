@@ -1,5 +1,5 @@
 // fks_gram.h -- the seed-basis Gram matrix on the torch_rocm stream (include/fks.h fks_gram): the
-// launch arguments fks_project.hip (the kernels) and fks_run.cpp (the driver) share, and the pass
+// launch arguments fks_project.hip (the kernels) and fks_run_basis.cpp (the driver) share, and the pass
 // size the planning of fks_phx.cpp tiles by.  A header of its own, not part of fks_internal.h:
 // fks_device.hip does not include it, so its object -- and fks_build_id() -- do not move with it.
 #pragma once

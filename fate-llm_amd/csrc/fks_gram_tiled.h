@@ -1,6 +1,6 @@
 // fks_gram_tiled.h -- the tiled seed-basis Gram matrix on the f64 matrix unit (include/fks.h
 // fks_gram_tiled; torch_rocm stream): the tile constants and launch arguments fks_gram_tiled.hip
-// (the kernels) and fks_run.cpp / fks_phx.cpp (the driver, the passes) share.  A header of its own
+// (the kernels) and fks_run_basis.cpp / fks_phx.cpp (the driver, the passes) share.  A header of its own
 // for fks_gram.h's reason: fks_device.hip does not include it, so its object -- and
 // fks_build_id() -- do not move with it.
 #pragma once

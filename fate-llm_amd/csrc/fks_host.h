@@ -1,6 +1,6 @@
 // fks_host.h -- host-internal declarations of libfks.so: fks_layout.cpp and fks_phx.cpp (pure
-// planning: no HIP, the device's CU count and grid cap are arguments), fks_cache.cpp, fks_run.cpp
-// and fks_capi.cpp.  Never included by a .hip file.
+// planning: no HIP, the device's CU count and grid cap are arguments), fks_cache.cpp, fks_run.cpp,
+// fks_run_basis.cpp and fks_capi.cpp.  Never included by a .hip file.
 #pragma once
 
 #include <algorithm>
@@ -335,6 +335,8 @@ void delta_apply(const fks_tensor* t, int nt, const float* delta, const double* 
                  size_t ws_bytes, void* stream);
 void digest(const fks_tensor* t, int nt, uint64_t pos0, uint64_t* dev_out2, void* stream);
 void device_selfcheck(int which, uint64_t* result, void* workspace, size_t ws_bytes, void* stream);
+
+// ================================================================== fks_run_basis.cpp
 // fks_project (vec: its one f32 vector, nvec 1) and fks_project_multi (vec null: vecs[nvec][nt])
 size_t project_ws_bytes(const fks_tensor* t, int nt, int nvec, bool multi);
 void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, const fks_vec* vecs,

@@ -1,0 +1,634 @@
+// fks_run_basis.cpp -- the launch drivers of the seed-basis calls (projection, Gram matrix and
+// expansion, each on the torch_rocm stream and on the CPU generator's).  Every driver keeps one
+// order: the geometry or layout on the host, the empty shard's exit, the workspace check, the
+// host tables -- so that every argument error is raised from the arguments alone, before anything
+// is allocated or launched (device_caps() reads the device's properties only and falls back to an
+// MI355X's without a device; tests/test_*_host.py run the calls that way) -- and only then
+// g_cache_mu, the plan, the upload and the launches, the lock held to the last of them.
+#include <cstdlib>
+
+#include "fks_run.h"
+
+namespace fks {
+namespace {
+
+void require_workspace(const void* workspace, size_t ws_bytes, size_t need) {
+  if (!workspace || ((uintptr_t)workspace % 8) != 0 || ws_bytes < need)
+    throw Error(-FKS_EINVAL, "workspace too small or misaligned: need " + std::to_string(need) + " bytes, got " +
+                                 std::to_string(ws_bytes));
+}
+
+// nothing in this shard: every sum is +0
+void zero_result(double* dev_out, size_t count, void* stream) {
+  check_hip(hipMemsetAsync(dev_out, 0, sizeof(double) * count, (hipStream_t)stream), "hipMemsetAsync");
+}
+
+// the tensors' first elements in the concatenation
+std::vector<int64_t> tensor_starts(const fks_tensor* t, int nt) {
+  std::vector<int64_t> start((size_t)nt, 0);
+  for (int i = 1; i < nt; i++) start[i] = start[i - 1] + t[i - 1].numel;
+  return start;
+}
+
+// ---- the torch_rocm stream ----
+// A call's element shard: the geometry on the host and the work items [lo, hi) the shard owns.
+struct PhxShard {
+  DevCaps dc;
+  PhxGeo geo;
+  int64_t lo = 0, hi = 0;
+  bool empty() const { return lo >= hi; }
+  int64_t items() const { return hi - lo; }
+  // the cached plan of the same geometry; under g_cache_mu, which the caller holds to its last launch
+  const PhxPlan* plan(const fks_tensor* t, int nt, uint64_t base) const {
+    const PhxPlan* P = get_phx_plan(t, nt, nullptr, base, dc);
+    if (P->nt != geo.nt) throw Error(-FKS_EINVAL, "torch_rocm plan does not match the call's geometry");
+    return P;
+  }
+};
+PhxShard phx_shard(const fks_tensor* t, int nt, uint64_t base, int shard, int nshards) {
+  PhxShard S;
+  S.dc = device_caps();
+  if (nt > 0) {
+    S.geo = phx_geometry(t, nt, nullptr, base, S.dc.max_grid);
+    S.lo = phx_boundary(S.geo, shard, nshards);
+    S.hi = phx_boundary(S.geo, shard + 1, nshards);
+  }
+  return S;
+}
+
+// Row m of out[nvec][geo.nt]: the piece of vector (output) m under every table entry -- a tensor
+// past 2^31 bytes has several entries.  vecs is [nvec][nt].
+void phx_vec_table(ProjVecEntry* out, const PhxGeo& geo, const fks_tensor* t, int nt, const fks_vec* vecs, int nvec) {
+  const std::vector<int64_t> start = tensor_starts(t, nt);
+  for (int m = 0; m < nvec; m++)
+    for (int e = 0; e < geo.nt; e++) {
+      const int i = geo.tensor_of[e];
+      const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+      ProjVecEntry& x = out[(size_t)m * (size_t)geo.nt + (size_t)e];
+      x.ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)(geo.elem0[e] - start[i]) * elem_size(v.dtype);
+      x.dtype = v.dtype;
+      x.flags = (x.ptr % 16u) == 0 ? kPhxP16 : 0u;
+    }
+}
+
+// ---- seed-basis projection (torch_rocm stream) ----
+// fks_project_multi's workspace: the vector table of the whole call ([nvec][entries], uploaded
+// once per call) in front, then the block partials of one pass of at most kProjMaxVec vectors
+size_t project_table_bytes(int entries, int nvec) {
+  return align_up(sizeof(ProjVecEntry) * (size_t)std::max(entries, 0) * (size_t)std::max(nvec, 0), 256);
+}
+// ... and the block partials a launch over `items` work items writes (fks_project.hip)
+size_t project_need(int64_t items, int entries, int nvec, bool multi) {
+  const size_t part = std::max<size_t>(sizeof(double) * (size_t)kPhxSeeds * (size_t)project_grid(items), 256);
+  return multi ? project_table_bytes(entries, nvec) + (size_t)std::min(std::max(nvec, 1), kProjMaxVec) * part : part;
+}
+
+}  // namespace
+
+// a shard walks at most the whole list's items; the passes of kPhxSeeds seeds follow
+// each other on the stream and share the partials
+size_t project_ws_bytes(const fks_tensor* t, int nt, int nvec, bool multi) {
+  const PhxGeo geo = phx_geometry(t, nt, nullptr, 0, device_caps().max_grid);
+  return project_need(geo.items, geo.nt, nvec, multi);
+}
+
+void project(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, const fks_vec* vecs,
+             int nvec, int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool multi = vec == nullptr;
+  // fks_project's table is fks_delta_accumulate's for this base; fks_project_multi's is geometry only
+  const uint64_t base = (uint64_t)(uintptr_t)vec;
+  const PhxShard S = phx_shard(t, nt, base, shard, nshards);
+  if (S.empty()) return zero_result(dev_out, (size_t)k * (size_t)nvec, stream);
+  const size_t tab_bytes = multi ? project_table_bytes(S.geo.nt, nvec) : 0;
+  require_workspace(workspace, ws_bytes, project_need(S.items(), S.geo.nt, nvec, multi));
+  thread_local std::vector<ProjVecEntry> host;  // the upload's source outlives the call
+  if (multi) {
+    host.assign((size_t)nvec * (size_t)S.geo.nt, ProjVecEntry{});
+    phx_vec_table(host.data(), S.geo, t, nt, vecs, nvec);
+  }
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = S.plan(t, nt, base);
+  if (multi)
+    check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjVecEntry) * host.size(), hipMemcpyHostToDevice,
+                             (hipStream_t)stream), "hipMemcpyAsync");
+  double* const partial = reinterpret_cast<double*>(static_cast<uint8_t*>(workspace) + tab_bytes);
+  const int grid = project_grid(S.items());
+  auto fill = [&](auto& a, int s0, int nb) {
+    a.t = static_cast<const PhxTensor*>(P->dev);
+    a.nt = P->nt;
+    a.partial = partial;
+    a.item_lo = S.lo;
+    a.item_hi = S.hi;
+    for (int j = 0; j < nb; j++) a.seeds[j] = seeds[s0 + j];
+    a.nseeds = nb;
+  };
+  for (int m0 = 0; m0 < nvec; m0 += kProjMaxVec) {  // batches of vectors over the same seeds
+    const int nv = std::min(kProjMaxVec, nvec - m0);
+    for (int s0 = 0; s0 < k; s0 += kPhxSeeds) {
+      const int nb = std::min(kPhxSeeds, k - s0);
+      if (multi) {
+        ProjectMultiArgs a{};
+        fill(a, s0, nb);
+        a.nvec = nv;
+        a.vt = static_cast<const ProjVecEntry*>(workspace) + (size_t)m0 * (size_t)P->nt;
+        check_launch(timed(0, stream, [&] { return launch_project_multi(a, stream); }), "fks_project_multi_kernel",
+                     "bad arguments");
+      } else {
+        ProjectArgs a{};
+        fill(a, s0, nb);
+        check_launch(timed(0, stream, [&] { return launch_project(a, stream); }), "fks_project_kernel",
+                     "bad arguments");
+      }
+      double* const out = dev_out + (size_t)m0 * (size_t)k + s0;
+      check_launch(launch_project_reduce(partial, grid, nb, nv, out, multi ? k : 0, stream),
+                   "fks_project_reduce_kernel", "bad arguments");
+    }
+  }
+}
+
+// ---- seed-basis Gram matrix (torch_rocm stream) ----
+// fks_gram and fks_gram_tiled are one driver over what differs: the tile.  The workspace holds the
+// block partials of ONE pass, Tile::cells doubles per workgroup of a launch over `items` work
+// items; the passes follow each other on the stream and share them.  Nothing depends on the seed
+// counts or has the model's size.
+namespace {
+
+struct GramTile {  // kGramRows x kPhxSeeds seeds (fks_gram.h), 1 KiB of partials per workgroup
+  using Args = GramArgs;
+  static constexpr size_t cells = (size_t)kGramRows * (size_t)kPhxSeeds;
+  static constexpr const char *kernel = "fks_gram_kernel", *reduce_kernel = "fks_gram_reduce_kernel";
+  static int grid(int64_t items) { return project_grid(items); }
+  static std::vector<GramPass> passes(int kr, int kc, bool symmetric) { return gram_passes(kr, kc, symmetric); }
+  static void pack(Args& a, const GramPass& p, const uint64_t* rows, const uint64_t* cols) {
+    for (int m = 0; m < kGramRows; m++) a.rseeds[m] = m < p.nrows ? rows[p.row0 + m] : 0;
+    for (int j = 0; j < p.ncols; j++) a.seeds[j] = cols[p.col0 + j];
+    a.nrows = p.nrows;
+    a.nseeds = p.ncols;
+  }
+  static int launch(const Args& a, void* stream) { return launch_gram(a, stream); }
+  static constexpr auto reduce = launch_gram_reduce;
+};
+
+struct GramMatrixTile {  // kGtRows x kGtCols seeds on the f64 matrix unit (fks_gram_tiled.h)
+  using Args = GramTiledArgs;
+  static constexpr size_t cells = (size_t)kGtTile;
+  static constexpr const char *kernel = "fks_gram_tiled_kernel", *reduce_kernel = "fks_gram_tiled_reduce_kernel";
+  static int grid(int64_t items) { return gram_tiled_grid(items); }
+  static std::vector<GramPass> passes(int kr, int kc, bool symmetric) { return gram_tiled_passes(kr, kc, symmetric); }
+  // seeds past a pass's counts are padded with 0 (drawn only where their 16-block is live, never written out)
+  static void pack(Args& a, const GramPass& p, const uint64_t* rows, const uint64_t* cols) {
+    for (int m = 0; m < kGtRows; m++) a.rseeds[m] = m < p.nrows ? rows[p.row0 + m] : 0;
+    for (int j = 0; j < kGtCols; j++) a.cseeds[j] = j < p.ncols ? cols[p.col0 + j] : 0;
+    a.nrb = (p.nrows + kGtSeeds - 1) / kGtSeeds;
+    a.ncb = (p.ncols + kGtSeeds - 1) / kGtSeeds;
+    // a column block that holds its row block's seeds takes the row block's operand (the diagonal
+    // tile of a symmetric call; the same values either way)
+    const int shared = std::min(a.nrb, a.ncb) * kGtSeeds;
+    a.diag = std::equal(a.rseeds, a.rseeds + shared, a.cseeds) ? 1 : 0;
+  }
+  static int launch(const Args& a, void* stream) { return launch_gram_tiled(a, stream); }
+  static constexpr auto reduce = launch_gram_tiled_reduce;
+};
+
+template <class Tile>
+size_t gram_need(int64_t items) {
+  return std::max<size_t>(sizeof(double) * Tile::cells * (size_t)Tile::grid(items), 256);
+}
+
+// per pass the kernel and the reduce with the matrix's addressing and the mirror
+template <class Tile>
+void gram_over(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+               int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  const PhxShard S = phx_shard(t, nt, 0, shard, nshards);
+  if (S.empty()) return zero_result(dev_out, (size_t)kr * (size_t)kc, stream);
+  require_workspace(workspace, ws_bytes, gram_need<Tile>(S.items()));
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = S.plan(t, nt, 0);
+  const int grid = Tile::grid(S.items());
+  typename Tile::Args a{};
+  a.t = static_cast<const PhxTensor*>(P->dev);
+  a.nt = P->nt;
+  a.partial = static_cast<double*>(workspace);
+  a.item_lo = S.lo;
+  a.item_hi = S.hi;
+  for (const GramPass& p : Tile::passes(kr, kc, symmetric)) {
+    Tile::pack(a, p, rows, cols);
+    check_launch(timed(0, stream, [&] { return Tile::launch(a, stream); }), Tile::kernel, "bad arguments");
+    check_launch(Tile::reduce(a.partial, grid, p.nrows, p.ncols, dev_out, kc, p.row0, p.col0, symmetric, stream),
+                 Tile::reduce_kernel, "bad arguments");
+  }
+}
+
+}  // namespace
+
+size_t gram_ws_bytes(const fks_tensor* t, int nt) {
+  return gram_need<GramTile>(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).items);
+}
+size_t gram_tiled_ws_bytes(const fks_tensor* t, int nt) {
+  return gram_need<GramMatrixTile>(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).items);
+}
+
+void gram(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+          int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  gram_over<GramTile>(t, nt, rows, kr, cols, kc, shard, nshards, dev_out, workspace, ws_bytes, stream);
+}
+void gram_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  gram_over<GramMatrixTile>(t, nt, rows, kr, cols, kc, shard, nshards, dev_out, workspace, ws_bytes, stream);
+}
+
+// ---- seed-basis expansion (torch_rocm stream) ----
+// fks_expand_multi's workspace, one per-call table uploaded in stream order: the outputs' pieces
+// ([nvec][entries] ProjVecEntry, a tensor past 2^31 bytes has several entries), the seeds ([k] u64),
+// then the coefficients as f32, per batch of kExpMaxVec outputs a block [k][outputs of the batch]
+struct ExpandWs {
+  size_t seeds_off = 0, coef_off = 0, total = 0;
+};
+static ExpandWs expand_ws(int entries, int k, int nvec) {
+  ExpandWs W;
+  W.seeds_off = project_table_bytes(entries, nvec);
+  W.coef_off = W.seeds_off + align_up(sizeof(uint64_t) * (size_t)std::max(k, 0), 256);
+  W.total = W.coef_off + align_up(sizeof(float) * (size_t)std::max(k, 0) * (size_t)std::max(nvec, 0), 256);
+  return W;
+}
+
+size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec) {
+  return expand_ws(phx_geometry(t, nt, nullptr, 0, device_caps().max_grid).nt, k, nvec).total;
+}
+
+// FKS_EXPAND_WORK (read per call): the seed-elements of one launch, an A/B and test switch
+int64_t expand_launch_work() {
+  if (const char* e = std::getenv("FKS_EXPAND_WORK")) {
+    char* end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    if (end != e && v > 0) return (int64_t)v;
+  }
+  return kExpLaunchWork;
+}
+
+void expand(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+            const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream) {
+  const PhxShard S = phx_shard(t, nt, 0, shard, nshards);
+  if (S.empty()) return;  // nothing in this shard
+  const ExpandWs W = expand_ws(S.geo.nt, k, nvec);
+  require_workspace(workspace, ws_bytes, W.total);
+  const std::vector<int64_t> cuts = phx_expand_cuts(S.geo, S.lo, S.hi, k, expand_launch_work());
+  thread_local std::vector<uint8_t> host;  // the upload's source outlives the call
+  host.assign(W.total, 0);
+  phx_vec_table(reinterpret_cast<ProjVecEntry*>(host.data()), S.geo, t, nt, outs, nvec);
+  if (k > 0) std::memcpy(host.data() + W.seeds_off, seeds, sizeof(uint64_t) * (size_t)k);
+  float* c = reinterpret_cast<float*>(host.data() + W.coef_off);
+  for (int m0 = 0; m0 < nvec; m0 += kExpMaxVec) {
+    const int nv = std::min(kExpMaxVec, nvec - m0);
+    float* blk = c + (size_t)k * (size_t)m0;
+    for (int s = 0; s < k; s++)
+      for (int m = 0; m < nv; m++) blk[(size_t)s * nv + m] = (float)coefs[(size_t)(m0 + m) * (size_t)k + s];
+  }
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const PhxPlan* P = S.plan(t, nt, 0);
+  check_hip(hipMemcpyAsync(workspace, host.data(), W.total, hipMemcpyHostToDevice, (hipStream_t)stream),
+            "hipMemcpyAsync");
+  const uint8_t* ws = static_cast<const uint8_t*>(workspace);
+  for (int m0 = 0; m0 < nvec; m0 += kExpMaxVec) {  // batches of outputs over the same seeds
+    ExpandArgs a{};
+    a.t = static_cast<const PhxTensor*>(P->dev);
+    a.nt = P->nt;
+    a.nvec = std::min(kExpMaxVec, nvec - m0);
+    a.ot = reinterpret_cast<const ProjVecEntry*>(ws) + (size_t)m0 * (size_t)P->nt;
+    a.seeds = reinterpret_cast<const uint64_t*>(ws + W.seeds_off);
+    a.coef = reinterpret_cast<const float*>(ws + W.coef_off) + (size_t)k * (size_t)m0;
+    a.nseeds = k;
+    for (int m = 0; m < a.nvec; m++) {
+      const double beta = betas ? betas[m0 + m] : 0.0;
+      a.beta[m] = (float)beta;
+      a.read_old |= beta != 0.0 ? 1u << m : 0u;
+    }
+    for (size_t c = 0; c + 1 < cuts.size(); c++) {  // launches of at most expand_launch_work() seed-elements
+      a.item_lo = cuts[c];
+      a.item_hi = cuts[c + 1];
+      check_launch(timed(0, stream, [&] { return launch_expand_multi(a, stream); }), "fks_expand_multi_kernel",
+                   "bad arguments");
+    }
+  }
+}
+
+// ---- the CPU generator's stream ----
+namespace {
+
+// The per-call table of the in-place calls over the geometry-only plan (the kModeDelta plan of
+// kProjMtGeoBase: one cache entry per tensor list and shard, whatever the vectors' addresses):
+// row m holds the piece of vector (output) m under every fast segment (the dtypes' segments
+// behind each other, as in the plan), run and single element of the shard's clipped layout.
+struct MtVecTable {
+  size_t segs[3] = {0, 0, 0}, nsegs = 0, nruns = 0, ntiny = 0;
+  size_t E = 0;  // entries of a row: nsegs + nruns + ntiny
+  // the cached plan has the descriptors the table was built for
+  bool matches(const CachedPlan& C) const {
+    bool same = (size_t)C.Z.nsegs == nsegs && (size_t)C.Z.nruns == nruns && (size_t)C.Z.ntiny == ntiny;
+    for (int d = 0; d < 3; d++) same = same && (size_t)C.nsegs[d] == segs[d];
+    return same;
+  }
+};
+// the table on the host, from the layout the plan is built from; vecs is [nvec][nt], `entries` what
+// the call's workspace layout allows a row
+MtVecTable mt_vec_table(std::vector<ProjMtVecEntry>& host, const fks_tensor* t, int nt, const fks_vec* vecs, int nvec,
+                        int shard, int nshards, int entries) {
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  clip_segments(L, shard_blocks(L.stream_len, shard, nshards));
+  MtVecTable T;
+  for (int d = 0; d < 3; d++) T.nsegs += T.segs[d] = L.segs[d].size();
+  T.nruns = L.runs.size();
+  T.ntiny = L.tiny.size();
+  T.E = T.nsegs + T.nruns + T.ntiny;
+  if (T.E != (size_t)entries) throw Error(-FKS_EINVAL, "the layout does not match the call's workspace layout");
+  const std::vector<int64_t> start = tensor_starts(t, nt);
+  host.assign((size_t)nvec * T.E, ProjMtVecEntry{});
+  for (int m = 0; m < nvec; m++) {
+    ProjMtVecEntry* x = host.data() + (size_t)m * T.E;
+    // a descriptor of tensor i whose element 0 is element (ptr - base) / 4 of the concatenation
+    auto put = [&](int i, uint64_t ptr) {
+      const fks_vec& v = vecs[(size_t)m * (size_t)nt + (size_t)i];
+      const int64_t e = (int64_t)((ptr - kProjMtGeoBase) / 4) - start[i];
+      x->ptr = (uint64_t)(uintptr_t)v.data + (uint64_t)e * elem_size(v.dtype);
+      x->dtype = v.dtype;
+      x++;
+    };
+    for (int d = 0; d < 3; d++)
+      for (size_t j = 0; j < L.segs[d].size(); j++) put(L.seg_tensor[d][j], L.segs[d][j].ptr);
+    for (size_t j = 0; j < L.runs.size(); j++) put(L.run_tensor[j], L.runs[j].ptr);
+    for (size_t j = 0; j < L.tiny.size(); j++) put(L.tiny_tensor[j], L.tiny[j].ptr);
+  }
+  return T;
+}
+
+const char* const kPlanMismatch = "the plan does not match the call's workspace layout";
+
+}  // namespace
+
+// ---- seed-basis projection (CPU generator's stream) ----
+// The plan fks_delta_accumulate launches for `vec` as its delta buffer; per pass of
+// kMaxSeedsPerPass seeds the regular jump, one launch per dtype with fast segments, the irregular
+// jump and launch, then the reduce over the rows all of them left.  No window, z-index or
+// reconstruct-window cache: the workspace holds the windows, the sink and the partial rows.
+void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const float* vec, int shard, int nshards,
+                double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ProjMtWs W = project_mt_ws(t, nt, k, shard, nshards, dc.cus);
+  if (!W.work) return zero_result(dev_out, (size_t)k, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, (uint64_t)(uintptr_t)vec, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const int rows = V.partial_rows();
+  if (rows < 1 || rows > W.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.partial_off)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  double* const partial = reinterpret_cast<double*>(ws + W.partial_off);
+  for (int s0 = 0; s0 < k; s0 += kMaxSeedsPerPass) {
+    const int nb = std::min(kMaxSeedsPerPass, k - s0);
+    double* row = partial;
+    if (C->have_reg) {
+      V.jump_regular(seeds + s0, nb, states);
+      V.each_fast_dtype([&](int d, int dd, size_t) {
+        ProjMtArgs pa{};
+        V.fill_fast(pa, d, states);
+        pa.sink = reinterpret_cast<const uint64_t*>(ws);
+        pa.partial = row;
+        pa.nseeds = nb;
+        check_launch(timed(0, stream, [&] { return launch_project_mt(dd, pa, stream); }), "fks_project_mt_kernel",
+                     "bad arguments");
+        row += (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+      });
+    }
+    if (C->have_irr) {
+      V.jump_irregular(seeds + s0, nb, states);
+      ProjMtIrrArgs ia{};
+      V.fill_irregular(ia, states);
+      ia.partial = row;
+      ia.nseeds = nb;
+      check_launch(timed(0, stream, [&] { return launch_project_mt_irr(ia, stream); }), "fks_project_mt_irr_kernel",
+                   "bad arguments");
+    }
+    check_launch(launch_project_reduce(partial, rows, nb, 1, dev_out + s0, 0, stream), "fks_project_reduce_kernel",
+                 "bad arguments");
+  }
+}
+
+// ---- ... of several vectors, each read where it lies ----
+// project_mt over the geometry-only plan and the per-call table at the front of the workspace,
+// uploaded in stream order.  The vectors go in batches of kProjMtMaxVec over the same seeds; a
+// batch of nv vectors takes its seeds in passes of proj_mt_pass_seeds(nv), each the launches of a
+// project_mt pass with rows of nv sums per seed.
+void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
+                      int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ProjMtMultiWs W = project_mt_multi_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.one.work) return zero_result(dev_out, (size_t)k * (size_t)nvec, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  const MtVecTable T = mt_vec_table(host, t, nt, vecs, nvec, shard, nshards, W.one.entries);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const int rows = V.partial_rows();
+  if (!T.matches(*C) || rows < 1 || rows > W.one.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.one.partial_off)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  uint8_t* ws = static_cast<uint8_t*>(workspace) + W.inner_off;
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  double* const partial = reinterpret_cast<double*>(ws + W.one.partial_off);
+  for (int m0 = 0; m0 < nvec; m0 += kProjMtMaxVec) {  // batches of vectors over the same seeds
+    const int nv = std::min(kProjMtMaxVec, nvec - m0);
+    const int per_pass = proj_mt_pass_seeds(nv);
+    const ProjMtVecEntry* tab = table + (size_t)m0 * T.E;
+    for (int s0 = 0; s0 < k; s0 += per_pass) {
+      const int nb = std::min(per_pass, k - s0);
+      double* row = partial;
+      if (C->have_reg) {
+        V.jump_regular(seeds + s0, nb, states);
+        V.each_fast_dtype([&](int d, int dd, size_t first) {
+          ProjMtMultiArgs pa{};
+          V.fill_fast(pa, d, states);
+          pa.sink = reinterpret_cast<const uint64_t*>(ws);
+          pa.partial = row;
+          pa.pv = tab + first;
+          pa.stride = (int64_t)T.E;
+          pa.nseeds = nb;
+          pa.nvec = nv;
+          check_launch(timed(0, stream, [&] { return launch_project_mt_multi(dd, pa, stream); }),
+                       "fks_project_mt_multi_kernel", "bad arguments");
+          row += (size_t)kPhxSeeds * (size_t)nv * (size_t)C->Z.reg_chunks;
+        });
+      }
+      if (C->have_irr) {
+        V.jump_irregular(seeds + s0, nb, states);
+        ProjMtIrrMultiArgs ia{};
+        V.fill_irregular(ia, states);
+        ia.partial = row;
+        ia.rv = tab + T.nsegs;
+        ia.tv = tab + T.nsegs + T.nruns;
+        ia.stride = (int64_t)T.E;
+        ia.nseeds = nb;
+        ia.nvec = nv;
+        check_launch(timed(0, stream, [&] { return launch_project_mt_irr_multi(ia, stream); }),
+                     "fks_project_mt_irr_multi_kernel", "bad arguments");
+      }
+      check_launch(launch_project_reduce(partial, rows, nb, nv, dev_out + (size_t)m0 * (size_t)k + s0, k, stream),
+                   "fks_project_reduce_kernel", "bad arguments");
+    }
+  }
+}
+
+// ---- seed-basis Gram matrix (CPU generator's stream) ----
+// gram's passes over project_mt_multi's geometry-only plan.  The windows of a pass lie in the
+// workspace as the kernels read them, the row tile's first and the column tile's behind them,
+// once at the regular and once at the irregular chunk starts: the row tile's are jumped when the
+// row tile begins and stay while its column tiles pass, the column tile's are jumped per pass.
+// Then the launches of a project_mt pass -- one per dtype with fast segments, the irregular one
+// -- and gram's reduce over the rows they left.  No per-call table: nothing is read.
+void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+             int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  const DevCaps dc = device_caps();
+  GramMtWs W;
+  if (nt > 0) W = gram_mt_ws(t, nt, shard, nshards, dc.cus);
+  if (!W.work) return zero_result(dev_out, (size_t)kr * (size_t)kc, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const int prows = V.partial_rows();
+  if (prows < 1 || prows > W.rows || (C->have_reg && C->Z.reg_chunks > W.reg_chunks) ||
+      (C->have_irr && C->Z.irr_chunks > W.irr_chunks))
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* const reg_states = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* const irr_states = reinterpret_cast<uint32_t*>(ws + W.irr_off);
+  double* const partial = reinterpret_cast<double*>(ws + W.partial_off);
+  // one seed's windows at the regular (irregular) chunk starts, in words
+  const size_t reg_win = (size_t)kMtN * (size_t)C->Z.reg_chunks, irr_win = (size_t)kMtN * (size_t)C->Z.irr_chunks;
+  int tile_row0 = -1;
+  for (const GramPass& p : gram_mt_passes(kr, kc, symmetric)) {
+    if (p.row0 != tile_row0) {  // a new row tile: its windows, once
+      tile_row0 = p.row0;
+      if (C->have_reg) V.jump_regular(rows + p.row0, p.nrows, reg_states);
+      if (C->have_irr) V.jump_irregular(rows + p.row0, p.nrows, irr_states);
+    }
+    double* row = partial;
+    if (C->have_reg) {
+      V.jump_regular(cols + p.col0, p.ncols, reg_states + (size_t)p.nrows * reg_win);
+      V.each_fast_dtype([&](int d, int dd, size_t) {
+        GramMtArgs ga{};
+        V.fill_fast(ga, d, reg_states);
+        ga.partial = row;
+        ga.nrows = p.nrows;
+        ga.ncols = p.ncols;
+        check_launch(timed(0, stream, [&] { return launch_gram_mt(dd, ga, stream); }), "fks_gram_mt_kernel",
+                     "bad arguments");
+        row += (size_t)kGramRows * (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+      });
+    }
+    if (C->have_irr) {
+      V.jump_irregular(cols + p.col0, p.ncols, irr_states + (size_t)p.nrows * irr_win);
+      GramMtIrrArgs ia{};
+      V.fill_irregular(ia, irr_states);
+      ia.partial = row;
+      ia.nseeds = p.nrows + p.ncols;
+      ia.nrows = p.nrows;
+      ia.ncols = p.ncols;
+      check_launch(timed(0, stream, [&] { return launch_gram_mt_irr(ia, stream); }), "fks_gram_mt_irr_kernel",
+                   "bad arguments");
+    }
+    check_launch(launch_gram_reduce(partial, prows, p.nrows, p.ncols, dev_out, kc, p.row0, p.col0, symmetric, stream),
+                 "fks_gram_reduce_kernel", "bad arguments");
+  }
+}
+
+// ---- seed-basis expansion (CPU generator's stream) ----
+// project_mt_multi's frame run the other way: the geometry-only plan, the per-call table of the
+// outputs' pieces at the front of the workspace, then per output the passes of kMaxSeedsPerPass
+// seeds -- the regular jump, one launch per dtype with fast segments, the irregular jump and
+// launch.  A call of more than one pass keeps one output's f32 sums in the staging area at the
+// back of the workspace between its passes (fks_expand_mt.h); k == 0 is one pass without seeds
+// (and so without jumps: MtPlan's jumps launch nothing for no seed).
+void expand_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+                     const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes,
+                     void* stream) {
+  const DevCaps dc = device_caps();
+  const ExpMtWs W = expand_mt_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.work) return;  // nothing in this shard
+  require_workspace(workspace, ws_bytes, W.total);
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  const MtVecTable T = mt_vec_table(host, t, nt, outs, nvec, shard, nshards, W.entries);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  if (!T.matches(*C) || (!C->have_reg && !C->have_irr) || (C->have_reg && C->Z.reg_chunks > W.reg_chunks) ||
+      (C->have_irr && C->Z.irr_chunks > W.irr_chunks))
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + W.win_off);
+  const uint64_t* sink = reinterpret_cast<const uint64_t*>(ws + W.sink_off);
+  const int passes = std::max(1, (k + kMaxSeedsPerPass - 1) / kMaxSeedsPerPass);
+  for (int m = 0; m < nvec; m++) {  // one output per pass of the generator
+    const ProjMtVecEntry* tab = table + (size_t)m * T.E;
+    const double beta = betas ? betas[m] : 0.0;
+    for (int p = 0; p < passes; p++) {
+      const int s0 = p * kMaxSeedsPerPass, nb = std::min(kMaxSeedsPerPass, k - s0);
+      ExpMtPass ps{};
+      for (int j = 0; j < nb; j++) ps.g[j] = (float)coefs[(size_t)m * (size_t)k + (size_t)(s0 + j)];
+      ps.stage_bias = (uint64_t)(uintptr_t)(ws + W.stage_off) - kProjMtGeoBase - 4u * (uint64_t)W.elem_lo;
+      ps.beta = (float)beta;
+      ps.nseeds = nb;
+      ps.carry_in = p > 0 ? 1 : 0;
+      ps.to_stage = p + 1 < passes ? 1 : 0;
+      ps.read_old = beta != 0.0 ? 1 : 0;
+      if (C->have_reg) {
+        V.jump_regular(seeds + s0, nb, states);
+        V.each_fast_dtype([&](int d, int dd, size_t first) {
+          ExpMtArgs ea{};
+          ea.p = ps;
+          V.fill_fast(ea, d, states);
+          ea.sink = sink;
+          ea.pv = tab + first;
+          check_launch(timed(0, stream, [&] { return launch_expand_mt(dd, ea, stream); }), "fks_expand_mt_kernel",
+                       "bad arguments");
+        });
+      }
+      if (C->have_irr) {
+        V.jump_irregular(seeds + s0, nb, states);
+        ExpMtIrrArgs ia{};
+        ia.p = ps;
+        V.fill_irregular(ia, states);
+        ia.rv = tab + T.nsegs;
+        ia.tv = tab + T.nsegs + T.nruns;
+        ia.nseeds = nb;
+        check_launch(timed(0, stream, [&] { return launch_expand_mt_irr(ia, stream); }), "fks_expand_mt_irr_kernel",
+                     "bad arguments");
+      }
+    }
+  }
+}
+
+}  // namespace fks

@@ -7,6 +7,7 @@ hit would still give the right parameters -- and the eviction of the two plan LR
 Launch counts come from codec.profile() (events around every jump and apply launch).
 Every sequence is also checked bit for bit against the oracle (torch_cpu stream) or
 torch's own ops on the device (torch_rocm stream)."""
+import ctypes
 import os
 
 import pytest
@@ -121,6 +122,101 @@ def test_reconstruct_launch_counts_torch_rocm():
     assert (prof.n_jump, prof.n_apply) == (0, 3)
     R.reconstruct(ref, seeds, vals, 1e-3, 0.0)
     assert torch.equal(got.view(torch.int16), ref[0].view(torch.int16))
+
+
+def _gram_pass_list(fn, kr, kc, symmetric):
+    """the (row0, nrows, col0, ncols) passes fks_gram*_passes reports for a call"""
+    from fate_llm.algo.fedkseed import _native as N
+    n = ctypes.c_int32(0)
+    N.check(fn(kr, kc, int(symmetric), None, 0, ctypes.byref(n)))
+    buf = (ctypes.c_int32 * (4 * n.value))()
+    N.check(fn(kr, kc, int(symmetric), buf, n.value, ctypes.byref(n)))
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(n.value)]
+
+
+def test_seed_basis_launch_counts():
+    """The seed-basis calls on list C (two dtypes with fast segments, irregular work): the jumps
+    and the timed launches of every driver are what its pass structure prescribes.  Per pass of the
+    torch_cpu stream, R + I = 2 jumps (the regular and the irregular chunk starts) and D + I = 3
+    launches (one per dtype with fast segments, the irregular one); the torch_rocm stream never
+    jumps.  The results themselves are the bit-for-bit tests' (test_gpu_project*.py, test_gpu_gram*.py,
+    test_gpu_expand*.py)."""
+    from fate_llm.algo.fedkseed import _native as N
+    from fate_llm.algo.fedkseed import codec
+    dev = _dev()
+    _clear()
+    L = N.load()
+    layout = LISTS["C"]
+    params = [from_np(a, dt, dev) for a, (dt, _) in zip(_arrays(layout), layout)]
+    specs = [codec.ParamSpec(p) for p in params]
+    k, nvec, jumps, launches = 20, 3, 2, 3
+    seeds, _ = _seeds_values(k)
+    g = torch.Generator().manual_seed(5)
+    vec = torch.randn(sum(n for _, n in layout), generator=g).to(dev)
+    vectors = [[torch.randn(n, generator=g).to(dev) for _, n in layout] for _ in range(nvec)]
+    coefs = torch.randn(nvec, k, generator=g, dtype=torch.float64).tolist()
+
+    def counts(call):
+        with codec.profile() as prof:
+            call()
+        torch.cuda.synchronize()
+        return prof.n_jump, prof.n_apply
+
+    def ceil(a, b):
+        return -(-a // b)
+
+    got, want = {}, {}
+    # ---- the torch_cpu stream
+    got["project_mt"] = counts(lambda: codec.project_mt(specs, seeds, vec))
+    want["project_mt"] = (ceil(k, 19) * jumps, ceil(k, 19) * launches)
+    # batches of PROJECT_MT_PASS_VECTORS vectors; a batch of one takes 19 seeds per pass, of two 10
+    # (csrc/fks_project_mt.h proj_mt_pass_seeds)
+    assert codec.PROJECT_MT_PASS_VECTORS == 2
+    passes = ceil(k, 10) + ceil(k, 19)
+    got["project_mt_multi"] = counts(lambda: codec.project_mt_multi(specs, seeds, vectors))
+    want["project_mt_multi"] = (passes * jumps, passes * launches)
+    for name, rows, cols in (("gram_mt 6", seeds[:6], None), ("gram_mt 5x7", seeds[:5], seeds[5:12])):
+        tiles = _gram_pass_list(L.fks_gram_mt_passes, len(rows), len(cols or rows), cols is None)
+        assert len(tiles) >= 2
+        got[name] = counts(lambda: codec.gram_mt(specs, rows, cols))
+        want[name] = ((len({t[0] for t in tiles}) + len(tiles)) * jumps, len(tiles) * launches)
+    outs = [[torch.empty_like(p) for p in params] for _ in range(nvec)]
+    got["expand_mt_multi"] = counts(lambda: codec.expand_mt_multi(specs, seeds, coefs, outs))
+    want["expand_mt_multi"] = (nvec * ceil(k, 19) * jumps, nvec * ceil(k, 19) * launches)
+    got["expand_mt_multi k=0"] = counts(lambda: codec.expand_mt_multi(specs, [], [[]] * nvec, outs))
+    want["expand_mt_multi k=0"] = (0, nvec * launches)  # one pass without seeds: nothing to jump
+    # ---- the torch_rocm stream: launches of at most 32 seeds, batches of at most four vectors or outputs
+    assert nvec <= min(codec.EXPAND_PASS_OUTPUTS, 4)
+    for kk in (k, 33):
+        s = _seeds_values(kk)[0]
+        got[f"project k={kk}"] = counts(lambda: codec.project(specs, s, vec, stream_mode="torch_rocm"))
+        got[f"project_multi k={kk}"] = counts(lambda: codec.project_multi(specs, s, vectors, stream_mode="torch_rocm"))
+        want[f"project k={kk}"] = want[f"project_multi k={kk}"] = (0, ceil(kk, 32))
+    for name, fn, sizes in (("gram", codec.gram, L.fks_gram_passes),
+                            ("gram_tiled", codec.gram_tiled, L.fks_gram_tiled_passes)):
+        for what, rows, cols in (("6", seeds[:6], None), ("5x7", seeds[:5], seeds[5:12])):
+            tiles = _gram_pass_list(sizes, len(rows), len(cols or rows), cols is None)
+            got[f"{name} {what}"] = counts(lambda: fn(specs, rows, cols, stream_mode="torch_rocm"))
+            want[f"{name} {what}"] = (0, len(tiles))
+    assert len(_gram_pass_list(L.fks_gram_passes, 6, 6, True)) >= 2
+    b = codec._Batch(specs, "torch_rocm", stage=False)
+    for work in (0, 1):  # the call's own bound (one launch here), then a single row per launch
+        ncuts, buf = ctypes.c_int32(0), (ctypes.c_int64 * 64)()
+        with torch.cuda.device(dev):
+            N.check(L.fks_expand_launch_cuts(ctypes.addressof(b.arr), b.n, k, 0, 1, work, 0, buf, 64,
+                                             ctypes.byref(ncuts)))
+        assert ncuts.value - 1 >= (2 if work else 1)
+        if work:
+            os.environ["FKS_EXPAND_WORK"] = str(work)
+        try:
+            got[f"expand_multi work {work}"] = counts(
+                lambda: codec.expand_multi(specs, seeds, coefs, outs, stream_mode="torch_rocm"))
+        finally:
+            os.environ.pop("FKS_EXPAND_WORK", None)
+        want[f"expand_multi work {work}"] = (0, ncuts.value - 1)
+    for name in want:
+        print(f"{name}: jumps, launches {got[name]}, prescribed {want[name]}")
+    assert got == want
 
 
 # ---- plan LRU eviction: 34 distinct lists against 32 entries ----
