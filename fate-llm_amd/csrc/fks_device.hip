@@ -58,10 +58,16 @@ constexpr int kBsFence = 8;      // slice kernel: compiler fence after every 8 s
 // -4.1 % per launch against the parent; the fma-free chain alone gains nothing, D = 8 with it 1.1 %, D = 8 and H1
 // 2.2-2.5 % (profiles/r10_bs_pos0_ab.log)
 #ifndef FKS_BS_LOOK              // D: the table lookups (loads only) of seed k + D are issued ahead of seed k's
-#define FKS_BS_LOOK 16           // arithmetic (0: at their seed; at most 32)
-#endif
+#define FKS_BS_LOOK 8            // arithmetic (0: at their seed; at most 32).  8 with eight waves per half; it was
+#endif                           // 16 with six (132 VGPRs: over the 128 that four waves per SIMD leave)
 #ifndef FKS_BS_H1                // 1: the twist's row and address arithmetic ahead of the flag poll, pinned in
 #define FKS_BS_H1 1              // VGPRs
+#endif
+// waves per half of the fma-free wd +0 chain's kernel (6, 7 or 8; every other chain: 6).  8 = four waves per SIMD,
+// at most 128 VGPRs: with FKS_BS_LOOK 8, 126 and no spill, -3.0 % per launch against six waves and LOOK 16; LOOK 12
+// -2.2 %, FKS_BS_R_VMEM 2 +0.9 %, seven waves +15 % (profiles/r17_bs_waves_ab.log)
+#ifndef FKS_BS_WAVES_POS0
+#define FKS_BS_WAVES_POS0 8
 #endif
 #ifndef FKS_PHX_VEC_ITEMS        // torch_rocm few-seed kernel: work items per thread (8; A/B: 4), see
 #define FKS_PHX_VEC_ITEMS 8      // kPhxVec in fks_kern_philox.h
@@ -188,10 +194,12 @@ int launch_apply(int dtype, const ApplyArgs& a, void* stream) {
 
 template <int MODE, bool FULL>
 static int launch_apply_bs_m(const ApplyBsArgs& a, void* stream) {
+  // the chain's wave count names the kernel, its block size and its LDS: one constant, no second source
+  constexpr int kWaves = bs_waves(MODE);
   static PerDevice attr;
-  if (int e = ensure_lds_attr(attr, &fks_apply_bs_kernel<MODE, FULL>, kBsLdsBytes)) return e;
-  hipLaunchKernelGGL((fks_apply_bs_kernel<MODE, FULL>), dim3((unsigned)(a.split ? a.nchunks / 2 : a.nchunks)),
-                     dim3(kBsThreads), kBsLdsBytes, (hipStream_t)stream, a);
+  if (int e = ensure_lds_attr(attr, &fks_apply_bs_kernel<MODE, FULL, kWaves>, bs_lds_bytes(kWaves))) return e;
+  hipLaunchKernelGGL((fks_apply_bs_kernel<MODE, FULL, kWaves>), dim3((unsigned)(a.split ? a.nchunks / 2 : a.nchunks)),
+                     dim3(bs_threads(kWaves)), bs_lds_bytes(kWaves), (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 

@@ -169,16 +169,18 @@ struct IrrArgs {
 };
 
 // bf16 slice kernel (fks_apply_bs_kernel): up to 64 seeds per pass; one workgroup per CU
-// with two bit-sliced 32-seed states (one plane word per 32 seeds) in two 384-thread
-// halves of six waves, each wave twisting and updating 128-word tasks; LDS = 3 KB of
+// with two bit-sliced 32-seed states (one plane word per 32 seeds) in two halves of W
+// waves (W = 6, 384 threads; a template parameter of the kernel, bs_waves() in
+// fks_kern_slice.h), each wave twisting and updating 128-word tasks; LDS = 3 KB of
 // tables + 2 x 79,872 B of state + task flags.  The plan cuts the stream into 2 x (one per
 // CU) chunks; a pass of 33..64 seeds runs two SLICES on one chunk PAIR (half 1 applies
 // seeds [ceil(n/2), n) after half 0 applied [0, ceil(n/2))), a pass of <= 32 seeds runs
 // one slice on each chunk of the pair (split).
 constexpr int kBsSeeds = 32;                  // seeds per slice (bits of a plane word)
 constexpr int kBsPassSeeds = 2 * kBsSeeds;    // seeds per launch
-constexpr int kBsHalfThreads = 384;
-constexpr int kBsThreads = 2 * kBsHalfThreads;
+constexpr int kBsWavesMin = 6, kBsWavesMax = 8;  // waves per half the kernel can be built for
+constexpr int bs_half_threads(int waves) { return 64 * waves; }
+constexpr int bs_threads(int waves) { return 2 * bs_half_threads(waves); }  // the block size
 constexpr int kBsChunksPerWg = 2;  // plan chunks per workgroup
 // reconstructs of more seeds than one 19-seed pass take the slice kernel for their
 // bf16 fast segments

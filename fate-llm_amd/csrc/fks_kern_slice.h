@@ -16,8 +16,10 @@ namespace {
 // as two SLICES of 32, generator state BIT-SLICED (fks_bitslice.h): row i of a slice's
 // state is state word i of its 32 seeds as 32 bit planes.  One workgroup per CU takes one
 // chunk and holds both slices' states in LDS, one per half.  The work of a chunk is cut
-// into TASKS of 128 consecutive stream words (64 Box-Muller pairs: one wave), and the six
-// waves of a half take the half's tasks round-robin.  A wave runs the whole of its task:
+// into TASKS of 128 consecutive stream words (64 Box-Muller pairs: one wave), and the W
+// waves of a half take the half's tasks round-robin (W: a template parameter, bs_waves()
+// below: 8 for the fma-free wd +0 chain, four waves per SIMD, 6 for every other chain).  A wave
+// runs the whole of its task:
 //   * twist: lane L owns the pair (j, j+8), j = 16 (L >> 3) + (L & 7) of the task, and
 //     twists exactly those two rows in place, block b -> b+1 (MT19937RNGEngine.h:164-175
 //     on 32 seeds at once): word u of the stream is f(word u-624 (plane 31 only: U31),
@@ -30,8 +32,8 @@ namespace {
 // previous task wrote -- so a wave waits until the half's LDS flag counts n twisted
 // tasks, twists task n, and publishes n+1; the chains of different tasks overlap freely.
 // Half 1 applies its seeds to what half 0 stored: its wave for task n waits until the
-// half-0 wave of task n+6 has published that store as complete before it prefetches
-// task n+6's parameters (half 0 publishes task m at its task m+6, after s_waitcnt
+// half-0 wave of task n+W has published that store as complete before it prefetches
+// task n+W's parameters (half 0 publishes task m at its task m+W, after s_waitcnt
 // vmcnt(0): workgroup-scope release; half 0 never waits for half 1).  Two slices per
 // workgroup instead of two chunks halve the jumps (one per seed and chunk) and the HBM
 // passes of a reconstruct.
@@ -43,7 +45,7 @@ namespace {
 // 3.83 -> 3.39 ms per 32-seed launch over 2^28 params (profiles/r03s_ab.log; the
 // variants measured on the way are in profiles/r03k..r03s_ab.log).
 // LDS: [R f32 x 256 | (C,S) f32 pairs x 256 | state half 0 | state half 1 | 2 twist flags |
-// 6 half-0 progress words]; a
+// W half-0 progress words | W half-1 progress words]; a
 // half's state is 8 CHUNK arrays (planes 4q..4q+3 of all 624 rows, 16 B per row), so a
 // row's chunk q is one ds_read_b128 / ds_write_b128.  The lane's first row is j+8 where
 // (L >> 3) is odd, which makes every 16-lane group of a ds_read_b128 (8-lane group of a
@@ -53,11 +55,20 @@ constexpr int kBsStateBytes = 8 * kBsChunkBytes;       // 79,872
 constexpr int kBsTabBytes = 256 * 4 + 256 * 8;         // 3,072
 constexpr uint32_t kBsFlagOff = kBsTabBytes + 2 * kBsStateBytes;  // u32 twisted-task count per half
 constexpr uint32_t kBsProgOff = kBsFlagOff + 8;        // u32 per half-0 wave: its tasks < value are stored
-constexpr uint32_t kBsProg1Off = kBsProgOff + 4 * 6;   // u32 per half-1 wave: its tasks < value are done
-constexpr int kBsLdsBytes = (int)kBsProg1Off + 4 * 6;  // 162,872 <= 163,840
-static_assert(kBsLdsBytes <= 163840, "slice kernel LDS");
-constexpr int kBsWaves = kBsHalfThreads / 64;          // waves per half (6)
 constexpr int kBsTaskWords = 128;                      // stream words per task
+// Waves per half, W: the kernel's third template parameter.  Everything that follows from it --
+// the block size and launch bounds, the task stride, the row step W * 128 mod 624, the progress
+// words and the LDS size -- is derived from it, in the kernel and in its launcher
+// (launch_apply_bs_m, fks_device.hip), and the instantiation of a chain is the one of
+// bs_waves(): a launch whose block size differs from the kernel's W does not exist.
+// Only the fma-free wd +0 chain has a switch (FKS_BS_WAVES_POS0, fks_device.hip).
+constexpr int bs_waves(int mode) { return mode == kModeUpdateWdPos0 ? FKS_BS_WAVES_POS0 : 6; }
+static_assert(FKS_BS_WAVES_POS0 >= kBsWavesMin && FKS_BS_WAVES_POS0 <= kBsWavesMax, "FKS_BS_WAVES_POS0");
+// u32 per half-1 wave: its tasks < value are done
+constexpr uint32_t bs_prog1_off(int waves) { return kBsProgOff + 4u * (uint32_t)waves; }
+// 162,872 for six waves, 162,888 for eight
+constexpr int bs_lds_bytes(int waves) { return (int)bs_prog1_off(waves) + 4 * waves; }
+static_assert(bs_lds_bytes(kBsWavesMax) <= 163840, "slice kernel LDS");
 
 // the 32 planes of row i (row byte address ra = state base + 16 i)
 __device__ __forceinline__ void bs_store_row(uint32_t ra, const uint32_t (&x)[32]) {
@@ -94,15 +105,20 @@ __device__ __forceinline__ uint32_t bs_index(uint32_t w, int c) {
 }
 
 #if FKS_BS_WGTIME  // diagnostic build: per-workgroup start and per-wave end times (100 MHz)
-__device__ uint64_t g_bs_wgtime[4096][16];
+constexpr int kBsWgtimeRow = 24;  // the start and up to 2 x kBsWavesMax ends (unused: 0)
+static_assert(1 + 2 * kBsWavesMax <= kBsWgtimeRow, "g_bs_wgtime");
+__device__ uint64_t g_bs_wgtime[4096][kBsWgtimeRow];
 extern "C" int fks_debug_bs_wgtime(uint64_t* out, int nblocks) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_wgtime), sizeof(uint64_t) * 16 * (size_t)nblocks, 0,
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_wgtime), sizeof(uint64_t) * kBsWgtimeRow * (size_t)nblocks, 0,
                                   hipMemcpyDeviceToHost);
 }
 #endif
 
-template <int MODE, bool FULL>
-__global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs a) {
+template <int MODE, bool FULL, int W>
+__global__ __launch_bounds__(bs_threads(W), 1) void fks_apply_bs_kernel(ApplyBsArgs a) {
+  static_assert(W == bs_waves(MODE), "one instantiation per chain: the launcher's");
+  constexpr int kBsWaves = W, kBsHalfThreads = bs_half_threads(W), kBsThreads = bs_threads(W);
+  constexpr uint32_t kBsProg1Off = bs_prog1_off(W);
   extern __shared__ __attribute__((aligned(16))) uint32_t lds32[];
   if ((uint32_t)(size_t)(lds_u32_t*)lds32 != 0u) __builtin_trap();
   const int tid = threadIdx.x;
@@ -272,9 +288,11 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // 4q+4 of chunk q+1, loaded one step ahead; U31 and V plane 0 are loaded first.  M
   // rows lie 227 words back, outside the task, so the task never stores them.
   // The state row of the lane's word toff of the wave's current task, (128 n + toff) mod 624.
-  // A wave's tasks lie kBsWaves * 128 = 768 words apart, so the row moves on by 144 mod 624:
-  // divided out once here and carried by next_row() from then on.
+  // A wave's tasks lie kBsWaves * 128 words apart (768 for six waves, 896, 1024), so the row moves
+  // on by that mod 624 (144, 272, 400): divided out once here and carried by next_row() from then
+  // on (row + kRowStep < 2 * 624, as wrap() needs).
   constexpr int kRowStep = kBsWaves * kBsTaskWords % kMtN;
+  static_assert(kMtN - 1 + kRowStep < 2 * kMtN, "next_row(): one wrap");
   int row = (kBsTaskWords * hw + toff) % kMtN;
   // kRowMin: the wraps as unsigned min -- x in [0, 2 * 624): min(x, x - 624) is x below 624
   // (x - 624 wraps to a huge value) and x - 624 from there on -- and the flip as the lane's
@@ -539,8 +557,8 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
   // behind that its loads of half 0's output came back from HBM (7.9 B/param per launch,
   // profiles/pmc_apply_r04_full.json).  Half 1 publishes each task as applied; half 0 waits
   // for task n - FKS_BS_LAG before twisting task n.  Half 1's task m needs half 0's task
-  // m + 2 kBsWaves (publish_stored), so the bound must exceed 2 kBsWaves = 12.
-  static_assert(FKS_BS_LAG == 0 || FKS_BS_LAG > 2 * kBsWaves, "FKS_BS_LAG: half 1 trails by 12 tasks");
+  // m + 2 kBsWaves (publish_stored), so the bound must exceed 2 kBsWaves (12 for six waves).
+  static_assert(FKS_BS_LAG == 0 || FKS_BS_LAG > 2 * kBsWaves, "FKS_BS_LAG: half 1 trails by 2 W tasks");
   // only the weight-decay chains need it: the wd 0 / None chains keep half 1 within L2 reach
   // unaided (4.17 B/param), and there the bound measured 1.4 % slower (profiles/r05d_ab_lag.log)
   constexpr bool kLag = FKS_BS_LAG > 0 && (MODE == kModeUpdateWd || MODE == kModeUpdate);
@@ -554,7 +572,7 @@ __global__ __launch_bounds__(kBsThreads, 1) void fks_apply_bs_kernel(ApplyBsArgs
     while (__builtin_amdgcn_readfirstlane(bs_flag_load(pm)) < (uint32_t)m + 1u) __builtin_amdgcn_s_sleep(1);
   };
 
-  // ---- task n: wait for task n-1's twist, twist, publish, chain; fetches task n + 6
+  // ---- task n: wait for task n-1's twist, twist, publish, chain; fetches task n + kBsWaves
   // into nx (past the last task: the sink)
   auto task = [&](const int n, const Slot& sl, Slot& nx) {
     uint32_t oa[8], ob[8];

@@ -43,7 +43,7 @@ def main():
     lib = ctypes.CDLL(LIB)
     lib.fks_debug_bs_wgtime.argtypes = [ctypes.c_void_p, ctypes.c_int]
     nblk = 256
-    buf = np.zeros((nblk, 16), dtype=np.uint64)
+    buf = np.zeros((nblk, 24), dtype=np.uint64)  # kBsWgtimeRow: the start, then one end per wave (unused: 0)
     codec.directional_step(specs, seeds[:64], vals[:64], shard=0, nshards=args.nshards)  # plan + warm-up
     torch.cuda.synchronize()
     for p in range(args.passes):
@@ -52,7 +52,7 @@ def main():
         torch.cuda.synchronize()
         assert lib.fks_debug_bs_wgtime(buf.ctypes.data, nblk) == 0
         start = buf[:, 0].astype(np.int64)
-        end = buf[:, 1:13].max(axis=1).astype(np.int64)
+        end = buf[:, 1:].max(axis=1).astype(np.int64)
         t0, t1 = start.min(), end.max()
         span = (t1 - t0) / 100.0  # us
         idle = float(np.mean(t1 - end)) / 100.0

@@ -13,7 +13,10 @@ GROUPS_=("SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTI
          "WRITE_SIZE GRBM_GUI_ACTIVE")
 for v in ${VARIANTS:-full}; do
   # full: the in-tree library at wd 0.01; wd0: the in-tree library at wd 0.0 (kModeUpdateWd0)
+  # NAME-wd0: the variant library ab/libfks_NAME.so at wd 0.0 (a parent build beside the in-tree one; not wd0_NAME,
+  # which the summaries' pmc2_wd0_* pattern would read as passes of wd0)
   if [ "$v" = "wd0" ]; then unset FKS_LIB_OVERRIDE; export PERF_WD=0.0
+  elif [ "${v%-wd0}" != "$v" ]; then export FKS_LIB_OVERRIDE=$PWD/fate-llm_amd/ab/libfks_${v%-wd0}.so; export PERF_WD=0.0
   elif [ "$v" != "full" ]; then export FKS_LIB_OVERRIDE=$PWD/fate-llm_amd/ab/libfks_$v.so; unset PERF_WD
   else unset FKS_LIB_OVERRIDE; unset PERF_WD; fi
   # the device-code identity of the library these passes profile (summarize_pmc2.py records it)

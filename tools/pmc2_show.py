@@ -22,7 +22,7 @@ def load(v, match):
 def main():
     kern = os.environ.get("KERNEL", "fks_apply_bs_kernel")
     vs = sys.argv[1:]
-    data = {v: load(v, lambda n: (kern + "<") in n and "true>" in n) for v in vs}
+    data = {v: load(v, lambda n: (kern + "<") in n and ", true" in n) for v in vs}
     names = sorted({k for d in data.values() for k in d})
     print("counter".ljust(26) + "".join(v.rjust(16) for v in vs))
     for n in names:

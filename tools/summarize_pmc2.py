@@ -17,7 +17,7 @@ KERNEL = "fks_apply_bs_kernel<"
 def _match(name, kernel):
     if kernel:
         return kernel in name
-    return KERNEL in name and "true>" in name
+    return KERNEL in name and ", true" in name  # <MODE, true> or <MODE, true, W>: the waves per half
 
 
 def per_pass(path, kernel=None):
