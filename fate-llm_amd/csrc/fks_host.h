@@ -15,6 +15,7 @@
 #include "fks_expand_mt.h"
 #include "fks_gram.h"
 #include "fks_gram_mt.h"
+#include "fks_gram_mt_tiled.h"
 #include "fks_gram_tiled.h"
 
 namespace fks {
@@ -150,6 +151,17 @@ struct GramMtWs {
   size_t irr_off = 0, partial_off = 0, total = 0;
 };
 GramMtWs gram_mt_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus);
+// fks_gram_mt_tiled's, bounds as above: [row block's and column block's windows at the regular
+// chunk starts | the same at the irregular chunk starts | the windows of one irregular sub-pass |
+// the fast launches' partial tiles | the irregular sub-passes' partial rows].  The seed counts do
+// not enter at all.
+struct GramMtTiledWs {
+  bool work = false;                   // the shard holds an element of a non-frozen tensor
+  int reg_chunks = 0, irr_chunks = 0;  // chunks of the plan's launches, at most
+  int reg_rows = 0;                    // partial tiles of one pass's fast launches, at most
+  size_t irr_off = 0, sub_off = 0, partial_off = 0, irr_partial_off = 0, total = 0;
+};
+GramMtTiledWs gram_mt_tiled_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -230,6 +242,8 @@ struct GramPass { int32_t row0, nrows, col0, ncols; };
 std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric);
 // fks_gram_mt's: the same order for its tile of kGramMtRows x kGramMtCols (fks_gram_mt.h)
 std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric);
+// fks_gram_mt_tiled's: the same order for its tile of kGmtTile x kGmtTile (fks_gram_mt_tiled.h)
+std::vector<GramPass> gram_mt_tiled_passes(int krows, int kcols, bool symmetric);
 // fks_gram_tiled's: the same order for its tile of kGtRows x kGtCols (fks_gram_tiled.h)
 std::vector<GramPass> gram_tiled_passes(int krows, int kcols, bool symmetric);
 
@@ -358,6 +372,9 @@ void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k,
 // fks_gram_mt: fks_gram on the CPU generator's stream, over the geometry-only plan
 void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
              int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_gram_mt_tiled: fks_gram_mt's matrix in passes of kGmtTile x kGmtTile seeds on the f64 matrix unit
+void gram_mt_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                   int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_expand_multi: nvec outputs written in place (outs[nvec][nt]), coefs[nvec][k], betas[nvec] or null
 int64_t expand_launch_work();  // kExpLaunchWork, or FKS_EXPAND_WORK where it is set to a positive number
 size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec);

@@ -385,6 +385,28 @@ GramMtWs gram_mt_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus
   return w;
 }
 
+// fks_gram_mt_tiled's workspace: fks_gram_mt's chunk counts with this call's tile.  The windows of
+// a row block and of a column block at the regular and at the irregular chunk starts (the row
+// block's stay while its column blocks pass), the windows of one irregular sub-pass laid out as
+// fks_gram_mt_irr_kernel reads them, one partial tile per chunk of every fast launch and one
+// partial row per chunk of every irregular sub-pass.  Nothing depends on the seed counts.
+GramMtTiledWs gram_mt_tiled_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus) {
+  const GramMtWs g = gram_mt_ws(t, nt, shard, nshards, cus);
+  GramMtTiledWs w;
+  w.work = g.work;
+  w.reg_chunks = g.reg_chunks;
+  w.irr_chunks = g.irr_chunks;
+  w.reg_rows = g.rows - g.irr_chunks;
+  const size_t win = sizeof(uint32_t) * kMtN;
+  const size_t irr = (size_t)std::max(w.irr_chunks, 1);
+  w.irr_off = align_up(win * kGmtWindows * (size_t)std::max(w.reg_chunks, 1), 256);
+  w.sub_off = w.irr_off + align_up(win * kGmtWindows * irr, 256);
+  w.partial_off = w.sub_off + align_up(win * (size_t)(kGramMtRows + kGramMtCols) * irr, 256);
+  w.irr_partial_off = w.partial_off + sizeof(double) * (size_t)kGmtCells * (size_t)std::max(w.reg_rows, 1);
+  w.total = w.irr_partial_off + sizeof(double) * (size_t)kGmtIrrCells * (size_t)kGmtSubs * irr;
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

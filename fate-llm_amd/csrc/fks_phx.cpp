@@ -184,6 +184,11 @@ std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric) {
   return gram_tile_passes(krows, kcols, symmetric, kGramMtRows, kGramMtCols);
 }
 
+// fks_gram_mt_tiled's passes: the same tiling by one 16-seed block each way (fks_gram_mt_tiled.h)
+std::vector<GramPass> gram_mt_tiled_passes(int krows, int kcols, bool symmetric) {
+  return gram_tile_passes(krows, kcols, symmetric, kGmtTile, kGmtTile);
+}
+
 // fks_gram_tiled's passes: the same tiling by its tile of kGtRows x kGtCols seeds (fks_gram_tiled.h;
 // columns >= rows)
 std::vector<GramPass> gram_tiled_passes(int krows, int kcols, bool symmetric) {

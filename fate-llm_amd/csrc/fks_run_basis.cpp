@@ -561,6 +561,103 @@ void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const ui
   }
 }
 
+// ---- tiled seed-basis Gram matrix (CPU generator's stream) ----
+// gram_mt's frame with a tile of kGmtTile x kGmtTile seeds: the row block's windows are jumped
+// when a row tile begins and kept while its column tiles pass, the column block's per pass; the
+// diagonal tile of a symmetric call has no column block of its own.  The fast segments go through
+// fks_gram_mt_tiled_kernel, one launch per dtype.  The irregular work goes through
+// fks_gram_mt_irr_kernel in sub-passes of ITS tile over the same windows -- jumped once per tile;
+// a sub-pass's windows are copied side by side, rows then columns, as that kernel reads them --,
+// each sub-pass into partial rows of its own.  The reduce adds a cell's partials in one order.
+void gram_mt_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                   int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  const DevCaps dc = device_caps();
+  GramMtTiledWs W;
+  if (nt > 0) W = gram_mt_tiled_ws(t, nt, shard, nshards, dc.cus);
+  if (!W.work) return zero_result(dev_out, (size_t)kr * (size_t)kc, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const int nirr = C->have_irr ? C->Z.irr_chunks : 0;
+  const int nreg = V.partial_rows() - nirr;
+  if (nreg + nirr < 1 || nreg > W.reg_rows || (C->have_reg && C->Z.reg_chunks > W.reg_chunks) || nirr > W.irr_chunks)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  // one seed's windows at the regular (irregular) chunk starts, in words
+  const size_t reg_win = (size_t)kMtN * (size_t)C->Z.reg_chunks, irr_win = (size_t)kMtN * (size_t)nirr;
+  uint32_t* const reg_rows = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* const reg_cols = reg_rows + (size_t)kGmtTile * reg_win;
+  uint32_t* const irr_rows = reinterpret_cast<uint32_t*>(ws + W.irr_off);
+  uint32_t* const irr_cols = irr_rows + (size_t)kGmtTile * irr_win;
+  uint32_t* const sub = reinterpret_cast<uint32_t*>(ws + W.sub_off);
+  double* const partial = reinterpret_cast<double*>(ws + W.partial_off);
+  double* const irr_partial = reinterpret_cast<double*>(ws + W.irr_partial_off);
+  auto copy_windows = [&](uint32_t* dst, const uint32_t* src, int n) {
+    check_hip(hipMemcpyAsync(dst, src, sizeof(uint32_t) * irr_win * (size_t)n, hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream), "hipMemcpyAsync");
+  };
+  int tile_row0 = -1;
+  for (const GramPass& p : gram_mt_tiled_passes(kr, kc, symmetric)) {
+    const bool diag = symmetric && p.col0 == p.row0;  // the column block holds the row block's seeds
+    if (p.row0 != tile_row0) {  // a new row tile: its windows, once
+      tile_row0 = p.row0;
+      if (C->have_reg) V.jump_regular(rows + p.row0, p.nrows, reg_rows);
+      if (C->have_irr) V.jump_irregular(rows + p.row0, p.nrows, irr_rows);
+    }
+    if (C->have_reg) {
+      if (!diag) V.jump_regular(cols + p.col0, p.ncols, reg_cols);
+      double* tile = partial;
+      V.each_fast_dtype([&](int d, int dd, size_t) {
+        GramMtTiledArgs ga{};
+        ga.row_states = reg_rows;
+        ga.col_states = diag ? nullptr : reg_cols;
+        ga.segs = V.at<DevSeg>(C->seg_off[d]);
+        ga.chunk_block = V.at<int64_t>(C->H.off_cb);
+        ga.partial = tile;
+        ga.nsegs = C->nsegs[d];
+        ga.nchunks = C->Z.reg_chunks;
+        ga.nrows = p.nrows;
+        ga.ncols = p.ncols;
+        ga.diag = diag ? 1 : 0;
+        check_launch(timed(0, stream, [&] { return launch_gram_mt_tiled(dd, ga, stream); }),
+                     "fks_gram_mt_tiled_kernel", "bad arguments");
+        tile += (size_t)kGmtCells * (size_t)C->Z.reg_chunks;
+      });
+    }
+    if (C->have_irr) {
+      if (!diag) V.jump_irregular(cols + p.col0, p.ncols, irr_cols);
+      const uint32_t* const col_src = diag ? irr_rows : irr_cols;
+      for (int m0 = 0; m0 < p.nrows; m0 += kGramMtRows) {
+        const int nr = std::min(kGramMtRows, p.nrows - m0);
+        copy_windows(sub, irr_rows + (size_t)m0 * irr_win, nr);
+        for (int n0 = 0; n0 < p.ncols; n0 += kGramMtCols) {
+          const int nc = std::min(kGramMtCols, p.ncols - n0);
+          copy_windows(sub + (size_t)nr * irr_win, col_src + (size_t)n0 * irr_win, nc);
+          GramMtIrrArgs ia{};
+          V.fill_irregular(ia, sub);
+          ia.partial = irr_partial + (size_t)kGmtIrrCells * (size_t)nirr *
+                                         (size_t)((m0 / kGramMtRows) * kGmtSubCols + n0 / kGramMtCols);
+          ia.nseeds = nr + nc;
+          ia.nrows = nr;
+          ia.ncols = nc;
+          check_launch(timed(0, stream, [&] { return launch_gram_mt_irr(ia, stream); }), "fks_gram_mt_irr_kernel",
+                       "bad arguments");
+        }
+      }
+    }
+    check_launch(launch_gram_mt_tiled_reduce(partial, nreg, irr_partial, nirr, p.nrows, p.ncols, dev_out, kc, p.row0,
+                                             p.col0, symmetric, stream),
+                 "fks_gram_mt_tiled_reduce_kernel", "bad arguments");
+  }
+}
+
 // ---- seed-basis expansion (CPU generator's stream) ----
 // project_mt_multi's frame run the other way: the geometry-only plan, the per-call table of the
 // outputs' pieces at the front of the workspace, then per output the passes of kMaxSeedsPerPass

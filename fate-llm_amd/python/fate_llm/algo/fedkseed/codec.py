@@ -882,7 +882,7 @@ def gram_tiled(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None,
     order or number, the place in a tile or the passes --, and the matrix is exactly symmetric.
     Returns the matrix on the specs' device, queued on the current stream.  No specs at all: zeros
     on the CPU.  Draws nothing from torch's generators.  torch_rocm stream only: a call that
-    resolves to torch_cpu raises NotImplementedError (``gram_mt`` is that stream's only form)."""
+    resolves to torch_cpu raises NotImplementedError (``gram_mt_tiled`` is that stream's tiled form)."""
     specs = list(specs)
     device = specs[0].tensor.device if specs else torch.device("cpu")
     mode = resolve_stream_mode(device, stream_mode)
@@ -962,6 +962,11 @@ def gram_mt(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, sh
     CPU path.  Returns the matrix on the specs' device, queued on the current stream; the plan is
     ``project_mt_multi``'s geometry-only one and the specs' data is not read.  No specs at all:
     zeros on the CPU.  Draws nothing from torch's generators and leaves the codec's caches alone."""
+    return _gram_mt_call(specs, seeds, col_seeds, shard, nshards, "fks_gram_mt")
+
+
+def _gram_mt_call(specs, seeds, col_seeds, shard, nshards, call):
+    """gram_mt and gram_mt_tiled: the two C calls share their arguments (``call`` names one)."""
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     b = _Batch(list(specs), "torch_cpu", stage=False)  # the specs' data is not read: no staging copies
@@ -976,13 +981,29 @@ def gram_mt(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, sh
     L = N.load()
     with torch.cuda.device(b.device):
         nbytes = ctypes.c_size_t(0)
-        N.check(L.fks_gram_mt_workspace_size(ctypes.addressof(b.arr), b.n, shape[0], shape[1], ctypes.byref(nbytes)))
+        N.check(getattr(L, call + "_workspace_size")(ctypes.addressof(b.arr), b.n, shape[0], shape[1],
+                                                     ctypes.byref(nbytes)))
         ws = torch.empty(max(int(nbytes.value), 1), dtype=torch.uint8, device=b.device)
-        N.check(L.fks_gram_mt(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
-                              None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1], int(shard),
-                              int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
-                              _stream_handle(b.device)))
+        N.check(getattr(L, call)(ctypes.addressof(b.arr), b.n, rows.ctypes.data, shape[0],
+                                 None if cols is None else cols.ctypes.data, 0 if cols is None else shape[1], int(shard),
+                                 int(nshards), out.data_ptr(), ws.data_ptr(), int(nbytes.value),
+                                 _stream_handle(b.device)))
     return out  # ws goes back to torch's allocator in stream order
+
+
+def gram_mt_tiled(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, shard: int = 0,
+                  nshards: int = 1) -> torch.Tensor:
+    """``gram_mt`` in tiles of 16 x 16 seeds on the f64 matrix unit (include/fks.h fks_gram_mt_tiled):
+    the same matrix on the torch_cpu stream, out[r, c] = <z_r, z_c> over the non-frozen specs'
+    elements that element shard ``shard`` of ``nshards`` owns, for seed counts where ``gram_mt``'s
+    passes of 4 x 5 seeds are too many.  Arguments, shapes and checks are ``gram_mt``'s.  Every
+    product is exact and every addition f64, in the kernel's own fixed order -- NOT ``gram_mt``'s:
+    the two agree to within 2 n 2^-52 sum|z_r z_c| over the n live elements, not bit for bit, and
+    this call has no bit-for-bit relation to ``project_mt_multi``.  out[r, c] depends on the
+    device, the spec list, the shard and its two seeds only -- not on the other seeds, their order
+    or number, the place in a tile or the passes --, and the matrix is exactly symmetric.  Draws
+    nothing from torch's generators and leaves the codec's caches alone."""
+    return _gram_mt_call(specs, seeds, col_seeds, shard, nshards, "fks_gram_mt_tiled")
 
 
 # outputs that share one pass of the generator in expand_multi (csrc/fks_expand.h kExpMaxVec;

@@ -399,7 +399,9 @@ def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_st
                                   f"this call resolves to the {mode} stream (fit_seed_scalars_exact_on_stream takes "
                                   "either stream)")
     b = _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
-    if tiled:
+    if tiled and on_stream and mode == "torch_cpu":
+        G = codec.gram_mt_tiled(specs, seeds)
+    elif tiled:
         G = codec.gram_tiled(specs, seeds, stream_mode=stream_mode)
     else:
         G = codec.gram_mt(specs, seeds) if mode == "torch_cpu" else codec.gram(specs, seeds, stream_mode=stream_mode)
@@ -472,6 +474,33 @@ def fit_seed_scalars_exact_on_stream(param_groups: List[dict], seeds: Sequence[i
     errors (a repeated seed, a Gram matrix that is not positive definite) are
     ``fit_seed_scalars_exact``'s.  The call SYNCHRONISES: G and b are copied to the host."""
     return _fit_exact("fit_seed_scalars_exact_on_stream", param_groups, seeds, delta_vector_lists, stream_mode, True)
+
+
+def seed_gram_tiled_on_stream(param_groups: List[dict], seeds: Sequence[int], col_seeds=None,
+                              stream_mode=None) -> torch.Tensor:
+    """``seed_gram_tiled`` on either stream: a call that resolves to torch_rocm takes
+    codec.gram_tiled (``seed_gram_tiled``'s bits), one that resolves to torch_cpu
+    codec.gram_mt_tiled -- the matrix of ``seed_gram_on_stream`` in passes of 16 x 16 seeds on the
+    f64 matrix unit, for seed counts in the hundreds and thousands on the CPU generator's stream.
+    G is exactly symmetric and reproducible, and agrees with ``seed_gram_on_stream`` to within
+    2 n 2^-52 sum|z_r z_c|, not bit for bit."""
+    params = [p for g in param_groups for p in g["params"]]
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    device = specs[0].tensor.device if specs else torch.device("cpu")
+    if codec.resolve_stream_mode(device, stream_mode) == "torch_cpu":
+        return codec.gram_mt_tiled(specs, seeds, col_seeds)
+    return codec.gram_tiled(specs, seeds, col_seeds, stream_mode=stream_mode)
+
+
+def fit_seed_scalars_exact_tiled_on_stream(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                                           stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars_exact_on_stream`` with G from the tiled calls: codec.gram_tiled on
+    torch_rocm (``fit_seed_scalars_exact_tiled``'s bits), codec.gram_mt_tiled on torch_cpu -- the
+    exact fit at the seed counts FedKSeed uses for a federation on the CPU generator's stream.
+    Arguments, result, errors and the synchronisation are ``fit_seed_scalars_exact``'s; the scalars
+    differ from ``fit_seed_scalars_exact_on_stream``'s by the f64 summation order of G only."""
+    return _fit_exact("fit_seed_scalars_exact_tiled_on_stream", param_groups, seeds, delta_vector_lists, stream_mode,
+                      True, tiled=True)
 
 
 def _expansion_outputs(params, outputs, m=None):

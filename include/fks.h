@@ -437,7 +437,7 @@ int fks_gram_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* pa
  * per CU -- the kernel's own residency -- at most: 8 MiB on 256 CUs), whatever krows and kcols.
  * Errors, raised from the arguments alone before any device work: those of fks_gram --
  * -FKS_EINVAL --; tensors of the CPU generator's stream (no FKS_STREAM_ROCM, with or without
- * FKS_LIBM): -FKS_ENOTSUP (fks_gram_mt is the only form for that stream).
+ * FKS_LIBM): -FKS_ENOTSUP (fks_gram_mt_tiled is the tiled call for that stream).
  * fks_gram_tiled_passes: fks_gram_passes for this call's tile (host arithmetic only).       */
 int fks_gram_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
 int fks_gram_tiled(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows,
@@ -554,6 +554,63 @@ int fks_gram_mt(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int3
                 int32_t kcols, int32_t shard, int32_t nshards, double* dev_out, void* workspace, size_t ws_bytes,
                 void* stream);
 int fks_gram_mt_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
+
+/* ---- tiled seed-basis Gram matrix on the CPU generator's stream (MT19937, f64 matrix unit) ----
+ * fks_gram_mt_tiled: fks_gram_mt's matrix for seed counts where fks_gram_mt's 4 x 5 passes are too
+ * many: a pass is a tile of 16 row seeds by 16 column seeds (v_mfma_f64_16x16x4_f64 forms the 256
+ * seed pairs from one draw per (seed, element)), so K = 4096 is 32,896 passes where fks_gram_mt
+ * makes about 420,000, and a pass draws 0.125 windows per cell where fks_gram_mt's draws 0.45.
+ * Arguments and output shape are fks_gram_mt's: dev_out[r * kc + c], r < krows, c < kc;
+ * col_seeds == NULL is the symmetric form (kcols 0 or krows, kc = krows, square output of row
+ * stride krows; the tile passes on and above the diagonal are computed and every element is also
+ * written to its transposed place), otherwise kc = kcols and the krows x kcols cells are computed
+ * as they stand.  Duplicate seeds are allowed.  Both sides are drawn inside the kernels: no
+ * vector is read, nothing of the model's size is written or allocated.
+ * Contract: dev_out[r * kc + c] is the sum over the non-frozen tensors i and the elements e that
+ * element shard `shard` of `nshards` owns of (double)z_{row_seeds[r]}(i, e) *
+ * (double)z_{col_seeds[c]}(i, e), with z_s(i, e) the value fks_normal writes for seed s on the
+ * CPU generator's stream in t[i].dtype (the FKS_LIBM flavour where the list carries it; the
+ * ragged head and the 16-word tail recompute, the serial numel < 16 draws with their cached
+ * second value).  Every product is exact in f64 and every addition is f64.  The ORDER of the
+ * additions is this kernel's own, one fixed order with no floating-point atomic: over the 16-
+ * aligned segments the matrix unit's order over the four elements of one MFMA, a wave's 32 MFMAs
+ * per MT block over its own 64 lanes' element pairs, the blocks of a plan chunk in order, the
+ * workgroup's five waves in wave order; then the chunks' partials of the pass's launches (one per
+ * dtype with such segments) followed by the chunks' partials of the irregular work -- scalar f64
+ * sums, fks_gram_mt's per cell -- in 16 interleaved runs, then the runs in order.  It is NOT
+ * fks_gram_mt's order: the two calls do not agree bit for bit, and fks_gram_mt_tiled has no
+ * bit-for-bit relation to fks_project_mt_multi.  Each is within n 2^-52 sum |z_r z_c| of the true
+ * sum over the n live elements of the shard, so the two agree to within 2 n 2^-52 sum |z_r z_c|.
+ * Reproducibility: an element depends on the device, the tensor list, the shard and its two
+ * seeds, and on nothing else -- not on the other seeds of the call, their order or their number,
+ * where in a tile the pair falls, nor how the call is cut into passes
+ * (fks_gram_mt_tiled_passes): the chunks are the plan's, and every accumulator of a tile sees the
+ * same sequence of operations.  Rows and columns that pad a pass to 16 enter +0 and are never
+ * written out.  <z_r, z_c> and <z_c, z_r> are the same products in the same order, so the matrix
+ * is exactly symmetric, whichever form computes it; the diagonal tile of a symmetric call takes
+ * the row block's draw as its column operand.  The shards are fks_project_mt's whole MT blocks;
+ * the shards' results add up to the whole call's.  Frozen tensors advance the stream and
+ * contribute nothing.  dev_out (krows * kc doubles, row-major, device memory, 8-byte aligned) is
+ * OVERWRITTEN in stream order, every element of it; an element written twice receives the same
+ * bits.  lr, wd and the other flags are ignored; the tensors' data pointers are not read.  Draws
+ * nothing from torch's generators; neither reads nor disturbs the one-seed window cache, the
+ * z-index buffer or the attached reconstruct window cache; uses fks_project_mt_multi's
+ * geometry-only plan.  krows == 0, kcols == 0 with column seeds given, nt == 0 and all-empty or
+ * all-frozen lists succeed; a shard with no element zeroes its output.
+ * Workspace: fks_gram_mt_tiled_workspace_size (8-byte aligned; a function of the list and the
+ * device's CU count, whatever krows and kcols): the generator windows of one row block and one
+ * column block at the plan's regular and irregular chunk starts (the row block's are jumped once
+ * per row tile and kept while its column tiles pass), the windows of one irregular sub-pass, and
+ * one pass's partials.
+ * Errors, raised from the arguments alone before any allocation or launch: those of fks_gram:
+ * -FKS_EINVAL; a list that carries FKS_STREAM_ROCM: -FKS_ENOTSUP (fks_gram_tiled is the call for
+ * that stream).
+ * fks_gram_mt_tiled_passes: fks_gram_passes for this call's tile (host arithmetic only).     */
+int fks_gram_mt_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
+int fks_gram_mt_tiled(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows,
+                      const uint64_t* col_seeds, int32_t kcols, int32_t shard, int32_t nshards, double* dev_out,
+                      void* workspace, size_t ws_bytes, void* stream);
+int fks_gram_mt_tiled_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
 
 /* ---- seed-basis expansion written in place (torch_rocm stream) ----
  * fks_expand_multi: the other direction of fks_project_multi, Z c instead of Z^T v: nvec dense
