@@ -11,6 +11,7 @@
 
 #include "fks_internal.h"
 #include "fks_project_mt.h"
+#include "fks_project_mt_bs.h"
 #include "fks_expand.h"
 #include "fks_expand_mt.h"
 #include "fks_gram.h"
@@ -129,6 +130,17 @@ struct ProjMtMultiWs {
   int pass_vec = 0;        // vectors per pass: min(nvec, kProjMtMaxVec), at least 1
 };
 ProjMtMultiWs project_mt_multi_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
+// fks_project_mt_bs's: [vector table: nvec x entries pieces | sink 4 KB | windows of one pass: the
+// bit-sliced launch's, then its 19-seed sub-passes' | the bit-sliced launch's rows [chunk][kBsPassSeeds]
+// | the sub-passes' rows [sub][row][kPhxSeeds]]; offsets behind the table count from inner_off
+struct ProjMtBsWs {
+  ProjMtWs one;            // the 19-seed launches' bounds: work, entries, rows of one sub-pass
+  int bs_chunks = 0;       // chunks of the slice kernel's plan (0: no bf16 fast segment), at most
+  int subs = 0;            // 19-seed sub-passes of one pass, at most
+  size_t inner_off = 0, bs_partial_off = 0, sub_partial_off = 0, total = 0;
+  size_t sub_stride = 0;   // doubles between two sub-passes' rows
+};
+ProjMtBsWs project_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
 // fks_expand_mt_multi's, for one shard's plan: [output table: nvec x entries pieces | generator
 // windows of one pass | sink 4 KB | f32 staging area of one output].  The staging area exists for
 // k > kMaxSeedsPerPass only and holds the elements of the concatenation from the first to the last
@@ -369,6 +381,9 @@ void project_mt(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const
 // fks_project_mt_multi: nvec vectors read in place (vecs[nvec][nt]) over the geometry-only plan
 void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
                       int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_project_mt_bs: the same sums in passes of kBsPassSeeds seeds, the bf16 fast segments bit-sliced
+void project_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec, int shard,
+                   int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_gram_mt: fks_gram on the CPU generator's stream, over the geometry-only plan
 void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
              int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);

@@ -407,6 +407,30 @@ GramMtTiledWs gram_mt_tiled_ws(const fks_tensor* t, int nt, int shard, int nshar
   return w;
 }
 
+// fks_project_mt_bs's workspace: the per-call table of vector pieces in front, as
+// fks_project_mt_multi's, then the sink, ONE window area -- the bit-sliced launch's windows of a
+// pass of min(k, kBsPassSeeds) seeds at every chunk start of the slice kernel's plan, which the
+// 19-seed sub-passes' windows then take over (the launches follow each other on the stream) --,
+// the bit-sliced launch's row per plan chunk and the rows of the sub-passes, each sub-pass its own.
+// A request of its own: no existing call's layout or plan moves with it.
+ProjMtBsWs project_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus) {
+  ProjMtBsWs w;
+  w.one = project_mt_ws(t, nt, k, shard, nshards, cus);
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  if (!L.segs[FKS_BF16].empty()) w.bs_chunks = bs_nchunks(br.hi - br.lo, cus);
+  const int pass = std::max(1, std::min(k, kBsPassSeeds));
+  w.subs = (pass + kMaxSeedsPerPass - 1) / kMaxSeedsPerPass;
+  w.inner_off = align_up(sizeof(ProjMtVecEntry) * (size_t)std::max(nvec, 0) * (size_t)w.one.entries, 256);
+  // (one.partial_off: the sink and the windows of a 19-seed pass over the larger of its chunk tables)
+  w.bs_partial_off = std::max(w.one.partial_off, align_up(ws_bytes_for(w.bs_chunks, pass), 256));
+  w.sub_partial_off = w.bs_partial_off + sizeof(double) * (size_t)kBsPassSeeds * (size_t)std::max(w.bs_chunks, 1);
+  w.sub_stride = (size_t)kPhxSeeds * (size_t)std::max(w.one.rows, 1);
+  w.total = w.inner_off + w.sub_partial_off + sizeof(double) * w.sub_stride * (size_t)w.subs;
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

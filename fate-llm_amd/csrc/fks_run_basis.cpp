@@ -491,6 +491,118 @@ void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k,
   }
 }
 
+// ---- ... bit-sliced, in passes of kBsPassSeeds seeds ----
+// project_mt_multi's plan and per-call table, the vectors one at a time over the same seeds.  A
+// pass of at most kBsPassSeeds seeds is one jump to EVERY chunk start of the slice kernel's plan
+// and one fks_project_mt_bs_kernel launch over the bf16 fast segments, whatever k; everything else
+// -- the other dtypes' fast segments and the irregular work (and the bf16 fast segments of a plan
+// without the slice kernel's chunk table) -- goes through project_mt_multi's one-vector launches
+// in sub-passes of kMaxSeedsPerPass seeds, each with its own jumps and its own partial rows.  One
+// reduce per pass adds a seed's rows in one order and overwrites its output.  No window, z-index
+// or reconstruct-window cache is read or written: every window lives in the workspace.
+void project_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec, int shard,
+                   int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ProjMtBsWs W = project_mt_bs_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.one.work) return zero_result(dev_out, (size_t)k * (size_t)nvec, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  const MtVecTable T = mt_vec_table(host, t, nt, vecs, nvec, shard, nshards, W.one.entries);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const bool bs = C->have_bs;  // the bf16 fast segments take the bit-sliced kernel
+  const int nbs = bs ? C->Z.bs_chunks : 0;
+  // the rows of one sub-pass: the other dtypes' fast launches, then the irregular one
+  int rows = C->have_irr ? C->Z.irr_chunks : 0;
+  bool reg_rest = false;
+  size_t bf16_first = 0;
+  V.each_fast_dtype([&](int d, int, size_t first) {
+    if (bs && d == FKS_BF16) {
+      bf16_first = first;
+      return;
+    }
+    rows += C->Z.reg_chunks;
+    reg_rest = true;
+  });
+  if (!T.matches(*C) || nbs + rows < 1 || nbs % 2 || nbs > W.bs_chunks || rows > W.one.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.one.partial_off)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint8_t* ws = static_cast<uint8_t*>(workspace) + W.inner_off;
+  const uint64_t* sink = reinterpret_cast<const uint64_t*>(ws);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  double* const bs_partial = reinterpret_cast<double*>(ws + W.bs_partial_off);
+  double* const sub_partial = reinterpret_cast<double*>(ws + W.sub_partial_off);
+  for (int m = 0; m < nvec; m++) {  // one vector per pass of the generator: the sums leave no room for two
+    const ProjMtVecEntry* tab = table + (size_t)m * T.E;
+    for (int s0 = 0; s0 < k; s0 += kBsPassSeeds) {
+      const int nb = std::min(kBsPassSeeds, k - s0);
+      if (bs) {
+        JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_bs_polys, C->H.off_bs_cb, states, nbs);
+        ja.stride = 1;  // every plan chunk, in both pass shapes: a (seed, chunk) sum has one form
+        ja.chunks_per_wg = std::max(1, std::min(nb * nbs >= 4096 ? 32 : 16, nbs));
+        check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+        ProjMtBsArgs ba{};
+        ba.states = states;
+        ba.segs = V.at<DevSeg>(C->seg_off[FKS_BF16]);
+        ba.chunk_block = ja.chunk_block;
+        ba.sink = sink;
+        ba.partial = bs_partial;
+        ba.pv = tab + bf16_first;
+        ba.nsegs = C->nsegs[FKS_BF16];
+        ba.nchunks = nbs;
+        ba.nseeds = nb;
+        ba.split = nb <= kBsSeeds ? 1 : 0;
+        check_launch(timed(0, stream, [&] { return launch_project_mt_bs(ba, stream); }), "fks_project_mt_bs_kernel",
+                     "bad arguments");
+      }
+      for (int u0 = 0; u0 < nb && rows > 0; u0 += kMaxSeedsPerPass) {  // the 19-seed launches' sub-passes
+        const int nu = std::min(kMaxSeedsPerPass, nb - u0);
+        const uint64_t* const sub_seeds = seeds + s0 + u0;
+        double* row = sub_partial + W.sub_stride * (size_t)(u0 / kMaxSeedsPerPass);
+        if (reg_rest) {
+          V.jump_regular(sub_seeds, nu, states);
+          V.each_fast_dtype([&](int d, int dd, size_t first) {
+            if (bs && d == FKS_BF16) return;
+            ProjMtMultiArgs pa{};
+            V.fill_fast(pa, d, states);
+            pa.sink = sink;
+            pa.partial = row;
+            pa.pv = tab + first;
+            pa.stride = (int64_t)T.E;
+            pa.nseeds = nu;
+            pa.nvec = 1;
+            check_launch(timed(0, stream, [&] { return launch_project_mt_multi(dd, pa, stream); }),
+                         "fks_project_mt_multi_kernel", "bad arguments");
+            row += (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+          });
+        }
+        if (C->have_irr) {
+          V.jump_irregular(sub_seeds, nu, states);
+          ProjMtIrrMultiArgs ia{};
+          V.fill_irregular(ia, states);
+          ia.partial = row;
+          ia.rv = tab + T.nsegs;
+          ia.tv = tab + T.nsegs + T.nruns;
+          ia.stride = (int64_t)T.E;
+          ia.nseeds = nu;
+          ia.nvec = 1;
+          check_launch(timed(0, stream, [&] { return launch_project_mt_irr_multi(ia, stream); }),
+                       "fks_project_mt_irr_multi_kernel", "bad arguments");
+        }
+      }
+      check_launch(launch_project_mt_bs_reduce(bs_partial, nbs, sub_partial, rows, (int64_t)W.sub_stride, nb,
+                                               dev_out + (size_t)m * (size_t)k + s0, stream),
+                   "fks_project_mt_bs_reduce_kernel", "bad arguments");
+    }
+  }
+}
+
 // ---- seed-basis Gram matrix (CPU generator's stream) ----
 // gram's passes over project_mt_multi's geometry-only plan.  The windows of a pass lie in the
 // workspace as the kernels read them, the row tile's first and the column tile's behind them,

@@ -337,6 +337,24 @@ def seed_projections_in_place(param_groups: List[dict], seeds: Sequence[int], ve
     return _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
 
 
+def seed_projections_bitsliced(param_groups: List[dict], seeds: Sequence[int], vector_lists=None,
+                               stream_mode=None) -> torch.Tensor:
+    """``seed_projections_in_place`` for many seeds, float64[M, K]: a call that resolves to
+    torch_cpu takes codec.project_mt_bs -- the bf16 parameters' draws bit-sliced, 64 seeds per pass
+    of the generator --, one that resolves to torch_rocm codec.project_multi, as
+    ``seed_projections_in_place`` routes.  ``vector_lists`` and the default (one list, every
+    parameter's ``.grad``) are that function's.  On torch_cpu the sums have codec.project_mt_bs's
+    own fixed order: row m equals the one-list call and column s the one-seed call bit for bit, and
+    every value lies within n 2^-52 sum |v z| of ``seed_projections_in_place``'s exact sum, whose
+    bits it does not share.  torch's generators are left alone."""
+    specs, vector_lists, _ = _projection_specs(param_groups, vector_lists)
+    if not specs:
+        return torch.zeros((len(vector_lists), len(seeds)), dtype=torch.float64)
+    if codec.resolve_stream_mode(specs[0].tensor.device, stream_mode) == "torch_cpu":
+        return codec.project_mt_bs(specs, seeds, vector_lists)
+    return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode)
+
+
 def fit_seed_scalars_in_place(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
                               stream_mode=None) -> torch.Tensor:
     """``fit_seed_scalars_multi`` on either stream: ``seed_projections_in_place / N``,

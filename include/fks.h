@@ -512,6 +512,38 @@ int fks_project_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds,
                          int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
                          size_t ws_bytes, void* stream);
 
+/* ---- ... bit-sliced, 64 seeds per pass ----
+ * fks_project_mt_bs: fks_project_mt_multi's sums with a contract of its own, for large k.  The
+ * arguments, the layout of vecs and dev_out ([nvec][k] doubles), the shards, the empty cases and
+ * the errors are exactly fks_project_mt_multi's (a list that carries FKS_STREAM_ROCM:
+ * -FKS_ENOTSUP).  The bf16 fast segments run on the bf16 slice kernel's bit-sliced generator, 32
+ * seeds per state and two states per workgroup, in passes of at most 64 seeds whatever k (also
+ * for k < 20); the f32 and f16 tensors and all irregular work run through fks_project_mt_multi's
+ * one-vector launches in sub-passes of 19 seeds.  The vectors go one at a time over the same seeds.
+ *   - dev_out[m * k + s] = sum over the shard's non-frozen elements e of (double)f32(vec_m[e]) *
+ *     (double)z_s(e), z_s what fks_normal writes for seeds[s] on this stream.
+ *   - Every product is exact in f64; the additions are f64 in this call's OWN fixed order (a
+ *     lane's fma chain over its elements of a plan chunk, the 64-lane butterfly, the half's waves
+ *     in wave order, then per seed the slice plan's chunks in chunk order and the rows of the
+ *     19-seed launches in fks_project_mt's row order; no floating-point atomic).  The result is
+ *     bit-reproducible for the same device, list, shard and seed, and lies within n 2^-52
+ *     sum |v z| of the exact sum (n the shard's elements).  It is NOT fks_project_mt's bits.
+ *   - Independence: dev_out[m * k + s] depends only on vector m's values, seeds[s], the list, the
+ *     shard and the device -- not on k, the seed's position, the other seeds, nvec, the vectors'
+ *     dtypes beyond their values, or their alignment.  A call with k seeds equals the k one-seed
+ *     calls, a call with nvec vectors the nvec one-vector calls, bit for bit.
+ *   - The shards' results add up to the whole call's (in f64, to rounding).
+ * dev_out is OVERWRITTEN in stream order.  The call reads and writes no window, z-index or
+ * reconstruct-window cache and uses fks_project_mt_multi's geometry-only plan.  Workspace:
+ * fks_project_mt_bs_workspace_size (8-byte aligned; a function of the list, k, nvec and the
+ * device's CU count alone; it grows with k up to 64 and is constant from there: 82,846,464 bytes
+ * on the 291-tensor 7B bf16 layout with one vector on 256 CUs -- 36,889,344 at k = 19 --, nearly
+ * all of it the 64 seeds' windows at the 512 chunk starts).                                    */
+int fks_project_mt_bs_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
+int fks_project_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
+                      int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
+                      size_t ws_bytes, void* stream);
+
 /* ---- seed-basis Gram matrix on the CPU generator's stream (MT19937) ----
  * fks_gram_mt: fks_gram's contract on fks_project_mt's stream.  dev_out[r * kc + c] = sum over
  * the non-frozen tensors i and the elements e that element shard `shard` of `nshards` owns of
