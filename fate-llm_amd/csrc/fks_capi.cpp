@@ -581,30 +581,65 @@ int fks_expand_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t 
   });
 }
 
+// fks_expand_mt_multi's argument checks, which fks_expand_mt_bs shares
+static void expand_mt_in_place_check(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs,
+                                     int32_t k, const fks_vec* outs, int32_t nvec, int32_t shard, int32_t nshards) {
+  validate(t, nt);
+  if (nvec < 0) throw Error(-FKS_EINVAL, "negative output count");
+  check_shard(shard, nshards);
+  if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
+  if (k > 0 && nvec > 0 && !coefs) throw Error(-FKS_EINVAL, "null coefficient array");
+  if (nvec > 0 && nt > 0 && !outs) throw Error(-FKS_EINVAL, "null output list");
+  for (int m = 0; m < nvec; m++)
+    for (int i = 0; i < nt; i++) {
+      if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
+      const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
+      if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
+        throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad output dtype " +
+                                     std::to_string(v.dtype));
+      if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
+        throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) +
+                                     ": null or misaligned output pointer");
+    }
+}
+
 int fks_expand_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
                         const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
                         void* workspace, size_t ws_bytes, void* stream) {
   return guarded([&] {
-    validate(t, nt);
-    if (nvec < 0) throw Error(-FKS_EINVAL, "negative output count");
-    check_shard(shard, nshards);
-    if (k < 0 || (k > 0 && !seeds)) throw Error(-FKS_EINVAL, "bad seed array");
-    if (k > 0 && nvec > 0 && !coefs) throw Error(-FKS_EINVAL, "null coefficient array");
-    if (nvec > 0 && nt > 0 && !outs) throw Error(-FKS_EINVAL, "null output list");
-    for (int m = 0; m < nvec; m++)
-      for (int i = 0; i < nt; i++) {
-        if (t[i].numel == 0 || (t[i].flags & FKS_FROZEN)) continue;  // ignored: may be NULL
-        const fks_vec& v = outs[(size_t)m * (size_t)nt + (size_t)i];
-        if (v.dtype != FKS_F32 && v.dtype != FKS_BF16 && v.dtype != FKS_F16)
-          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) + ": bad output dtype " +
-                                       std::to_string(v.dtype));
-        if (!v.data || ((uintptr_t)v.data % elem_size(v.dtype)) != 0)
-          throw Error(-FKS_EINVAL, "output " + std::to_string(m) + ", tensor " + std::to_string(i) +
-                                       ": null or misaligned output pointer");
-      }
+    expand_mt_in_place_check(t, nt, seeds, coefs, k, outs, nvec, shard, nshards);
     expand_mt_check_stream(t, nt);
     if (nvec == 0 || nt == 0) return;
     expand_mt_multi(t, nt, seeds, coefs, k, outs, betas, nvec, shard, nshards, workspace, ws_bytes, stream);
+  });
+}
+
+// ... bit-sliced, the bf16 fast segments in passes of 32 seeds
+static void expand_mt_bs_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_expand_mt_bs: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_expand_multi is the call for that stream");
+}
+
+int fks_expand_mt_bs_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, int32_t shard,
+                                    int32_t nshards, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    check_shard(shard, nshards);
+    expand_mt_bs_check_stream(t, nt);
+    *bytes = expand_mt_bs_ws(t, nt, k, nvec, shard, nshards, device_cu_count()).total;
+  });
+}
+
+int fks_expand_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                     const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                     void* workspace, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    expand_mt_in_place_check(t, nt, seeds, coefs, k, outs, nvec, shard, nshards);
+    expand_mt_bs_check_stream(t, nt);
+    if (nvec == 0 || nt == 0) return;
+    expand_mt_bs(t, nt, seeds, coefs, k, outs, betas, nvec, shard, nshards, workspace, ws_bytes, stream);
   });
 }
 

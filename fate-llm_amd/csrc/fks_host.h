@@ -14,6 +14,7 @@
 #include "fks_project_mt_bs.h"
 #include "fks_expand.h"
 #include "fks_expand_mt.h"
+#include "fks_expand_mt_bs.h"
 #include "fks_gram.h"
 #include "fks_gram_mt.h"
 #include "fks_gram_mt_tiled.h"
@@ -153,6 +154,18 @@ struct ExpMtWs {
   size_t win_off = 0, sink_off = 0, stage_off = 0, stage_bytes = 0, total = 0;
 };
 ExpMtWs expand_mt_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
+// fks_expand_mt_bs's, for one shard's plan: fks_expand_mt_multi's order -- [output table | generator
+// windows of one pass | sink 4 KB | f32 staging area of one output] -- with ONE window area for the
+// larger of a bit-sliced pass (min(k, kBsSeeds) seeds at every chunk start of the slice kernel's
+// plan) and a 19-seed pass, which follow each other on the stream.  The staging area exists where
+// one of the two pass sequences needs a second pass: k > kBsSeeds, or k > kMaxSeedsPerPass with
+// anything but bf16 fast segments under the slice kernel's plan in the shard.
+struct ExpMtBsWs {
+  ExpMtWs one;             // fks_expand_mt_multi's bounds: work, entries, chunks, the span
+  int bs_chunks = 0;       // chunks of the slice kernel's plan (0: the bf16 fast segments take the 19-seed launches)
+  size_t win_off = 0, sink_off = 0, stage_off = 0, stage_bytes = 0, total = 0;
+};
+ExpMtBsWs expand_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
 // fks_gram_mt's, for one shard's plan (bounds; shard 0 of 1 bounds every shard): [row tile's and
 // column tile's windows at the regular chunk starts | the same at the irregular chunk starts |
 // partial rows of one pass].  The seed counts enter as min(k, tile) only.
@@ -399,5 +412,8 @@ void expand(const fks_tensor* t, int nt, const uint64_t* seeds, const double* co
 void expand_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
                      const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes,
                      void* stream);
+// fks_expand_mt_bs: the same bits, the bf16 fast segments bit-sliced in passes of kBsSeeds seeds
+void expand_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+                  const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream);
 
 }  // namespace fks

@@ -431,6 +431,39 @@ ProjMtBsWs project_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int sh
   return w;
 }
 
+// fks_expand_mt_bs's workspace: fks_expand_mt_multi's with one window area for both pass sequences
+// and the staging area wherever one of them runs a second pass.  The slice kernel's plan is the one
+// plan_image builds for the shard (the same chunk count and the same 2^31-word limit on a chunk
+// pair); without it the bf16 fast segments count among the 19-seed work.  A request of its own: no
+// existing call's layout or plan moves with it.
+ExpMtBsWs expand_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus) {
+  ExpMtBsWs w;
+  w.one = expand_mt_ws(t, nt, k, nvec, shard, nshards, cus);
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  if (k > 0 && !L.segs[FKS_BF16].empty()) {
+    const std::vector<int64_t> bcb = chunk_table(br, bs_nchunks(br.hi - br.lo, cus));
+    const int n = (int)bcb.size() - 1;
+    w.bs_chunks = n;
+    for (int c = 0; c < n; c++)
+      if ((bcb[(size_t)std::min(c + 2, n)] - bcb[(size_t)c]) * kMtN >= ((int64_t)1 << 31)) w.bs_chunks = 0;
+  }
+  const bool rest = !w.bs_chunks ? w.one.work
+                                 : !L.segs[FKS_F32].empty() || !L.segs[FKS_F16].empty() || !L.runs.empty() || !L.tiny.empty();
+  const size_t seed_win = sizeof(uint32_t) * kMtN;
+  const size_t win19 = seed_win * (size_t)std::max(0, std::min(k, kMaxSeedsPerPass)) *
+                       (size_t)std::max({w.one.reg_chunks, w.one.irr_chunks, 1});
+  const size_t win32 = seed_win * (size_t)std::max(0, std::min(k, kBsSeeds)) * (size_t)w.bs_chunks;
+  const bool staged = k > kBsSeeds || (k > kMaxSeedsPerPass && rest);
+  w.win_off = w.one.win_off;  // the table
+  w.sink_off = w.win_off + align_up(std::max(win19, win32), 256);
+  w.stage_off = w.sink_off + kWsStatesOff;
+  w.stage_bytes = staged ? sizeof(float) * (size_t)(w.one.elem_hi - w.one.elem_lo) : 0;
+  w.total = w.stage_off + w.stage_bytes;
+  return w;
+}
+
 uint64_t fnv1a(const std::vector<uint8_t>& b) {
   uint64_t h = 1469598103934665603ull;
   for (uint8_t c : b) h = (h ^ c) * 1099511628211ull;

@@ -840,4 +840,116 @@ void expand_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, const d
   }
 }
 
+// ---- ... bit-sliced, the bf16 fast segments in passes of kBsSeeds seeds ----
+// expand_mt_multi's frame -- the geometry-only plan, the per-call table, one output at a time --
+// with two independent pass sequences over disjoint elements of the output: the bf16 fast segments
+// under the slice kernel's chunk table in passes of kBsSeeds (one jump to EVERY chunk start, one
+// fks_expand_mt_bs_kernel launch), everything else in passes of kMaxSeedsPerPass through
+// expand_mt_multi's own launches.  Each sequence has its own carry_in / to_stage; both stage at
+// ExpMtPass's addresses, so one area serves, and one window area, since the launches follow each
+// other on the stream.  Without seeds, or without the chunk table, the bf16 fast segments take the
+// 19-seed launches too: expand_mt_multi's path.
+void expand_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, const double* coefs, int k, const fks_vec* outs,
+                  const double* betas, int nvec, int shard, int nshards, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ExpMtBsWs W = expand_mt_bs_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.one.work) return;  // nothing in this shard
+  require_workspace(workspace, ws_bytes, W.total);
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  const MtVecTable T = mt_vec_table(host, t, nt, outs, nvec, shard, nshards, W.one.entries);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const bool bs = C->have_bs && k > 0;  // the bf16 fast segments take the bit-sliced kernel
+  const int nbs = bs ? C->Z.bs_chunks : 0;
+  if (!T.matches(*C) || (!C->have_reg && !C->have_irr) || (C->have_reg && C->Z.reg_chunks > W.one.reg_chunks) ||
+      (C->have_irr && C->Z.irr_chunks > W.one.irr_chunks) || nbs % 2 || nbs > W.bs_chunks || (bs && nbs < 2))
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + W.win_off);
+  const uint64_t* sink = reinterpret_cast<const uint64_t*>(ws + W.sink_off);
+  const uint64_t stage_bias = (uint64_t)(uintptr_t)(ws + W.stage_off) - kProjMtGeoBase - 4u * (uint64_t)W.one.elem_lo;
+  // the 19-seed launches' share of the fast segments, and whether they have any work at all
+  bool reg_rest = false;
+  size_t bf16_first = 0;
+  V.each_fast_dtype([&](int d, int, size_t first) {
+    if (bs && d == FKS_BF16) bf16_first = first;
+    else reg_rest = true;
+  });
+  const bool rest = reg_rest || C->have_irr;
+  if ((bs && k > kBsSeeds && !W.stage_bytes) || (rest && k > kMaxSeedsPerPass && !W.stage_bytes))
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  const int bs_passes = bs ? (k + kBsSeeds - 1) / kBsSeeds : 0;
+  const int passes = rest ? std::max(1, (k + kMaxSeedsPerPass - 1) / kMaxSeedsPerPass) : 0;
+  for (int m = 0; m < nvec; m++) {  // one output per pass of the generator
+    const ProjMtVecEntry* tab = table + (size_t)m * T.E;
+    const double beta = betas ? betas[m] : 0.0;
+    const double* const cm = coefs + (size_t)m * (size_t)k;
+    for (int p = 0; p < bs_passes; p++) {  // the bf16 fast segments, kBsSeeds seeds a pass
+      const int s0 = p * kBsSeeds, nb = std::min(kBsSeeds, k - s0);
+      JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_bs_polys, C->H.off_bs_cb, states, nbs);
+      ja.stride = 1;  // every plan chunk: a half runs one
+      ja.chunks_per_wg = std::max(1, std::min(nb * nbs >= 4096 ? 32 : 16, nbs));
+      check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+      ExpMtBsArgs ba{};
+      for (int j = 0; j < nb; j++) ba.g[j] = (float)cm[s0 + j];
+      ba.states = states;
+      ba.segs = V.at<DevSeg>(C->seg_off[FKS_BF16]);
+      ba.chunk_block = ja.chunk_block;
+      ba.sink = sink;
+      ba.pv = tab + bf16_first;
+      ba.stage_bias = stage_bias;
+      ba.beta = (float)beta;
+      ba.nseeds = nb;
+      ba.carry_in = p > 0 ? 1 : 0;
+      ba.to_stage = p + 1 < bs_passes ? 1 : 0;
+      ba.read_old = beta != 0.0 ? 1 : 0;
+      ba.nsegs = C->nsegs[FKS_BF16];
+      ba.nchunks = nbs;
+      check_launch(timed(0, stream, [&] { return launch_expand_mt_bs(ba, stream); }), "fks_expand_mt_bs_kernel",
+                   "bad arguments");
+    }
+    for (int p = 0; p < passes; p++) {  // everything else, exactly as expand_mt_multi issues it
+      const int s0 = p * kMaxSeedsPerPass, nb = std::min(kMaxSeedsPerPass, k - s0);
+      ExpMtPass ps{};
+      for (int j = 0; j < nb; j++) ps.g[j] = (float)cm[s0 + j];
+      ps.stage_bias = stage_bias;
+      ps.beta = (float)beta;
+      ps.nseeds = nb;
+      ps.carry_in = p > 0 ? 1 : 0;
+      ps.to_stage = p + 1 < passes ? 1 : 0;
+      ps.read_old = beta != 0.0 ? 1 : 0;
+      if (reg_rest) {
+        V.jump_regular(seeds + s0, nb, states);
+        V.each_fast_dtype([&](int d, int dd, size_t first) {
+          if (bs && d == FKS_BF16) return;
+          ExpMtArgs ea{};
+          ea.p = ps;
+          V.fill_fast(ea, d, states);
+          ea.sink = sink;
+          ea.pv = tab + first;
+          check_launch(timed(0, stream, [&] { return launch_expand_mt(dd, ea, stream); }), "fks_expand_mt_kernel",
+                       "bad arguments");
+        });
+      }
+      if (C->have_irr) {
+        V.jump_irregular(seeds + s0, nb, states);
+        ExpMtIrrArgs ia{};
+        ia.p = ps;
+        V.fill_irregular(ia, states);
+        ia.rv = tab + T.nsegs;
+        ia.tv = tab + T.nsegs + T.nruns;
+        ia.nseeds = nb;
+        check_launch(timed(0, stream, [&] { return launch_expand_mt_irr(ia, stream); }), "fks_expand_mt_irr_kernel",
+                     "bad arguments");
+      }
+    }
+  }
+}
+
 }  // namespace fks

@@ -36,6 +36,7 @@ EXPORTED = (
     "fks_project_mt_bs_workspace_size", "fks_project_mt_bs",
     "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
     "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
+    "fks_expand_mt_bs_workspace_size", "fks_expand_mt_bs",
     "fks_gram_workspace_size", "fks_gram", "fks_gram_passes",
     "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
     "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes",
@@ -141,6 +142,8 @@ def load():
                                              ctypes.POINTER(c_i32)]
         L.fks_expand_mt_multi_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_expand_mt_multi.argtypes = [P, c_i32, P, P, c_i32, P, P, c_i32, c_i32, c_i32, P, c_sz, P]
+        L.fks_expand_mt_bs_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_expand_mt_bs.argtypes = [P, c_i32, P, P, c_i32, P, P, c_i32, c_i32, c_i32, P, c_sz, P]
         L.fks_gram_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_gram.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         L.fks_gram_passes.argtypes = [c_i32, c_i32, c_i32, P, c_i32, ctypes.POINTER(c_i32)]
@@ -166,6 +169,7 @@ def load():
                      "fks_project_mt_bs_workspace_size", "fks_project_mt_bs",
                      "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
                      "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
+                     "fks_expand_mt_bs_workspace_size", "fks_expand_mt_bs",
                      "fks_gram_workspace_size", "fks_gram", "fks_gram_passes",
                      "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
                      "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes",

@@ -1132,18 +1132,29 @@ EXPAND_MT_STAGING_MIN = 1 << 30
 EXPAND_MT_STAGING_SPLIT = 8
 
 
-def _expand_mt_sizes(b: "_Batch", K: int, M: int, nshards: int):
-    """Per shard of ``nshards``: (workspace bytes, staging bytes of them) of fks_expand_mt_multi.
-    The table and the windows do not grow past one pass's seeds, so the staging area is what a
-    call of K seeds needs beyond a call of one pass.  Host arithmetic only."""
+def _expand_mt_sizes(b: "_Batch", K: int, M: int, nshards: int, bitsliced: bool = False):
+    """Per shard of ``nshards``: (workspace bytes, staging bytes of them) of fks_expand_mt_multi, or
+    of fks_expand_mt_bs.  The table and the windows do not grow past one pass's seeds, so the
+    staging area is what fks_expand_mt_multi's call of K seeds needs beyond a call of one pass.  The
+    bit-sliced call stages the same span: past 32 seeds, and past 19 where the shard holds more than
+    bf16 fast segments -- where its 33rd seed adds nothing to its workspace.  Host arithmetic only."""
     L = N.load()
+
+    def size(fn, k, sh):
+        nbytes = ctypes.c_size_t(0)
+        N.check(fn(ctypes.addressof(b.arr), b.n, k, M, sh, nshards, ctypes.byref(nbytes)))
+        return int(nbytes.value)
+
+    multi, bs = L.fks_expand_mt_multi_workspace_size, L.fks_expand_mt_bs_workspace_size
     out = []
     for sh in range(nshards):
-        full, one = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        N.check(L.fks_expand_mt_multi_workspace_size(ctypes.addressof(b.arr), b.n, K, M, sh, nshards, ctypes.byref(full)))
-        N.check(L.fks_expand_mt_multi_workspace_size(ctypes.addressof(b.arr), b.n, min(K, EXPAND_MT_PASS_SEEDS), M, sh,
-                                                     nshards, ctypes.byref(one)))
-        out.append((int(full.value), int(full.value) - int(one.value)))
+        full = size(multi, K, sh)
+        span = full - size(multi, min(K, EXPAND_MT_PASS_SEEDS), sh)
+        if not bitsliced:
+            out.append((full, span))
+        else:
+            staged = K > 32 or (K > EXPAND_MT_PASS_SEEDS and size(bs, 33, sh) == size(bs, 32, sh))
+            out.append((size(bs, K, sh), span if staged else 0))
     return out
 
 
@@ -1169,6 +1180,25 @@ def expand_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, out
     depend on the split.  A smaller explicit budget is honoured and may cost more cached plans.
     With ``nshards > 1`` the caller has split already and ``staging_bytes`` is not consulted.
     Asynchronous on the current stream; draws nothing from torch's generators."""
+    _expand_mt_in_place(specs, seeds, coefs, outputs, betas, shard, nshards, staging_bytes)
+
+
+def expand_mt_bs(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, outputs, betas=None, shard: int = 0,
+                 nshards: int = 1, staging_bytes: Optional[int] = None) -> None:
+    """``expand_mt_multi`` for many seeds (include/fks.h fks_expand_mt_bs): the same arguments,
+    argument checks, internal split into element shards under ``staging_bytes`` and keep-alive,
+    and the same BITS in every element of every output -- the chain is elementwise and ordered and
+    an f32 store between two seeds loses nothing, so it does not matter how the seeds are cut into
+    passes.  The bf16 specs' fast segments run bit-sliced, 32 seeds per generator state and pass;
+    fp32 and fp16 specs and all irregular work take ``expand_mt_multi``'s launches, 19 seeds at a
+    time.  Up to 32 seeds over bf16 specs alone need no staging area.  Nothing routes here by K:
+    DESIGN.md 4.2 has the measured rates of the two calls.  Asynchronous on the current stream;
+    draws nothing from torch's generators and leaves them and every attached cache alone."""
+    _expand_mt_in_place(specs, seeds, coefs, outputs, betas, shard, nshards, staging_bytes, bitsliced=True)
+
+
+def _expand_mt_in_place(specs, seeds, coefs, outputs, betas, shard, nshards, staging_bytes, bitsliced=False) -> None:
+    """expand_mt_multi and expand_mt_bs behind their shared checks and shard split."""
     specs = list(specs)
     outputs = [list(o) for o in outputs]
     c, bt = _expand_arguments(specs, seeds, coefs, outputs, betas, shard, nshards)
@@ -1188,7 +1218,8 @@ def expand_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, out
             oarr[m * n + i].dtype = _DTYPES[o.dtype]
     L = N.load()
     calls = [(int(shard), int(nshards))]
-    sizes = _expand_mt_sizes(b, K, M, int(nshards))[int(shard):int(shard) + 1]
+    fn = L.fks_expand_mt_bs if bitsliced else L.fks_expand_mt_multi
+    sizes = _expand_mt_sizes(b, K, M, int(nshards), bitsliced)[int(shard):int(shard) + 1]
     if nshards == 1 and K > EXPAND_MT_PASS_SEEDS:
         whole = sizes[0][1]
         budget = (max(EXPAND_MT_STAGING_MIN, -(-whole // EXPAND_MT_STAGING_SPLIT)) if staging_bytes is None
@@ -1200,7 +1231,7 @@ def expand_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, out
         while ns > 1:  # the smallest shard count whose largest staging area fits (a shard's area shrinks with the count)
             if ns > blocks:
                 raise ValueError(f"staging_bytes {budget}: no split of the list into element shards stages so little")
-            sizes = _expand_mt_sizes(b, K, M, ns)
+            sizes = _expand_mt_sizes(b, K, M, ns, bitsliced)
             if max(st for _, st in sizes) <= budget:
                 break
             ns += 1
@@ -1209,9 +1240,8 @@ def expand_mt_multi(specs: Sequence[ParamSpec], seeds: Sequence[int], coefs, out
     with torch.cuda.device(b.device):
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=b.device)
         for sh, ns in calls:
-            N.check(L.fks_expand_mt_multi(ctypes.addressof(b.arr), b.n, s.ctypes.data if K else None,
-                                          c.ctypes.data if K else None, K, ctypes.addressof(oarr), bt.ctypes.data, M,
-                                          sh, ns, ws.data_ptr(), nbytes, _stream_handle(b.device)))
+            N.check(fn(ctypes.addressof(b.arr), b.n, s.ctypes.data if K else None, c.ctypes.data if K else None, K,
+                       ctypes.addressof(oarr), bt.ctypes.data, M, sh, ns, ws.data_ptr(), nbytes, _stream_handle(b.device)))
     # queued: ws goes back to torch's allocator in stream order
 
 

@@ -600,6 +600,11 @@ def seed_expansions_on_stream_(param_groups: List[dict], seeds: Sequence[int], s
     g z of a local step lands in ``.grad`` with no buffer beyond the generator windows --; more
     seeds run through a bounded f32 staging area (codec.expand_mt_multi).  Row m equals the
     single call bit for bit; torch's generators are left alone."""
+    return _expansions_on_stream_(param_groups, seeds, scalar_lists, output_lists, accumulate, stream_mode, False)
+
+
+def _expansions_on_stream_(param_groups, seeds, scalar_lists, output_lists, accumulate, stream_mode, bitsliced):
+    """seed_expansions_on_stream_ and seed_expansions_bitsliced_: the torch_cpu call differs."""
     params = [p for g in param_groups for p in g["params"]]
     if not params or codec.resolve_stream_mode(params[0].device, stream_mode) != "torch_cpu":
         return seed_expansions_(param_groups, seeds, scalar_lists, output_lists, accumulate=accumulate,
@@ -618,8 +623,27 @@ def seed_expansions_on_stream_(param_groups: List[dict], seeds: Sequence[int], s
     specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
     betas = [1.0 if accumulate else 0.0] * len(outs)
     detached = [[None if o is None else o.detach() for o in os_] for os_ in outs]
-    codec.expand_mt_multi(specs, seeds, scalar_lists, detached, betas=betas)
+    (codec.expand_mt_bs if bitsliced else codec.expand_mt_multi)(specs, seeds, scalar_lists, detached, betas=betas)
     return outs
+
+
+def seed_expansions_bitsliced_(param_groups: List[dict], seeds: Sequence[int], scalar_lists, output_lists,
+                               accumulate: bool = False, stream_mode=None):
+    """``seed_expansions_on_stream_`` for many seeds: a call that resolves to torch_cpu takes
+    codec.expand_mt_bs -- the bf16 parameters' draws bit-sliced, 32 seeds per pass of the generator
+    --, one that resolves to torch_rocm codec.expand_multi, as ``seed_expansions_on_stream_``
+    routes.  Arguments, defaults and the result are that function's, and so is every bit of every
+    output: the two torch_cpu calls differ in how the seeds are cut into passes, which the f32 chain
+    does not see.  torch's generators are left alone."""
+    return _expansions_on_stream_(param_groups, seeds, scalar_lists, output_lists, accumulate, stream_mode, True)
+
+
+def seed_expansion_bitsliced_(param_groups: List[dict], seeds: Sequence[int], scalars: Sequence[float], outputs=None,
+                              accumulate: bool = False, stream_mode=None):
+    """``seed_expansions_bitsliced_`` for one output, as ``seed_expansion_on_stream_`` is
+    ``seed_expansions_on_stream_``'s.  Returns the list of outputs."""
+    return seed_expansions_bitsliced_(param_groups, seeds, [list(scalars)], [outputs], accumulate=accumulate,
+                                      stream_mode=stream_mode)[0]
 
 
 def seed_expansion_on_stream_(param_groups: List[dict], seeds: Sequence[int], scalars: Sequence[float], outputs=None,

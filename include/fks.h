@@ -730,6 +730,38 @@ int fks_expand_mt_multi(const fks_tensor* t, int32_t nt, const uint64_t* seeds, 
                         const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
                         void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- ... bit-sliced, 32 seeds per pass over the bf16 tensors ----
+ * fks_expand_mt_bs: fks_expand_mt_multi's arguments and fks_expand_mt_multi's BITS, for large k:
+ * every element of every output is the same, for every dtype of tensor and output, every k, beta,
+ * shard and alignment.  The chain of the contract above is elementwise and ordered --
+ *   acc = +0.0f;  for s in order: acc = fmaf((float)c_s, z_s, acc);  then cast(acc), or
+ *   cast(fmaf(beta, widen(old), acc)) --
+ * and an f32 store between two seeds loses nothing, so the bits do not depend on how the seeds are
+ * cut into passes.  The bf16 tensors' fast segments run on the bf16 slice kernel's bit-sliced
+ * generator, 32 seeds per state and pass, two states (two plan chunks) per workgroup, whatever k >
+ * 0; the f32 and f16 tensors and all irregular work run through fks_expand_mt_multi's own launches
+ * in passes of 19, and so do the bf16 fast segments where k == 0 or a chunk pair of the slice
+ * kernel's plan is 2^31 stream words long or longer.  The two pass sequences work on disjoint
+ * elements of one output and share the windows and the staging area.  Everything else is as
+ * fks_expand_mt_multi states it: frozen tensors advance the stream and are not written; with beta
+ * 0 the old output is never read; zero coefficients are not skipped; a seed past k takes no part
+ * (a sum of -0 stays -0); k == 0 writes +0 where beta is 0; nothing is drawn from torch's
+ * generators; no window, z-index or reconstruct-window cache is touched; the tensors' data
+ * pointers are not read; the plan is fks_project_mt_multi's geometry-only one.  Workspace, in
+ * order: the per-call table, the windows (the larger of one bit-sliced pass of min(k, 32) seeds at
+ * every chunk start of the slice kernel's plan and one 19-seed pass), the sink, the staging area
+ * -- 4 bytes per element of the shard's span, present where a sequence needs a second pass: k > 32,
+ * or k > 19 with anything but such bf16 fast segments in the shard:
+ * fks_expand_mt_bs_workspace_size for the same k, nvec, shard and nshards (8-byte aligned).
+ * Errors are fks_expand_mt_multi's, raised from the arguments alone before any allocation or
+ * launch: -FKS_EINVAL; a list that carries FKS_STREAM_ROCM: -FKS_ENOTSUP.  No other call routes
+ * here.                                                                                        */
+int fks_expand_mt_bs_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, int32_t shard,
+                                    int32_t nshards, size_t* bytes);
+int fks_expand_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* seeds, const double* coefs, int32_t k,
+                     const fks_vec* outs, const double* betas, int32_t nvec, int32_t shard, int32_t nshards,
+                     void* workspace, size_t ws_bytes, void* stream);
+
 /* torch.manual_seed(seed); for every tensor in order: p = torch.normal(0, 1, size, dtype). */
 int fks_normal(const fks_tensor* t, int32_t nt, uint64_t seed, void* workspace, size_t ws_bytes, void* stream);
 
