@@ -18,6 +18,7 @@
 #include "fks_gram.h"
 #include "fks_gram_mt.h"
 #include "fks_gram_mt_tiled.h"
+#include "fks_gram_mt_bs.h"
 #include "fks_gram_tiled.h"
 
 namespace fks {
@@ -187,6 +188,16 @@ struct GramMtTiledWs {
   size_t irr_off = 0, sub_off = 0, partial_off = 0, irr_partial_off = 0, total = 0;
 };
 GramMtTiledWs gram_mt_tiled_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus);
+// fks_gram_mt_bs's, bounds as above: [fks_gram_mt_tiled's layout, for one 16 x 16 tile of a pass at
+// a time | the windows of one pass's kGmbsPassSeeds seeds at the slice plan's chunk starts | the
+// bit-sliced launch's partial tiles [chunk][kGmbsDiagTiles][kGmtCells]].  The seed counts do not
+// enter at all.
+struct GramMtBsWs {
+  GramMtTiledWs one;       // fks_gram_mt_tiled's bounds and offsets
+  int bs_chunks = 0;       // chunks of the slice kernel's plan (0: the bf16 fast segments take one's launches)
+  size_t bs_states_off = 0, bs_partial_off = 0, total = 0;
+};
+GramMtBsWs gram_mt_bs_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus);
 
 // the weight-decay form all of a launch's descriptors (segments, Philox entries) share, or kModeUpdate
 template <class D>
@@ -269,6 +280,10 @@ std::vector<GramPass> gram_passes(int krows, int kcols, bool symmetric);
 std::vector<GramPass> gram_mt_passes(int krows, int kcols, bool symmetric);
 // fks_gram_mt_tiled's: the same order for its tile of kGmtTile x kGmtTile (fks_gram_mt_tiled.h)
 std::vector<GramPass> gram_mt_tiled_passes(int krows, int kcols, bool symmetric);
+// fks_gram_mt_bs's (fks_layout.cpp): a symmetric call's pass with col0 == row0 is a DIAGONAL pass of
+// nrows == ncols <= kGmbsPassSeeds consecutive seeds, every other pass a PAIR pass of at most
+// kGmtTile x kGmtTile (fks_gram_mt_bs.h)
+std::vector<GramPass> gram_mt_bs_passes(int krows, int kcols, bool symmetric);
 // fks_gram_tiled's: the same order for its tile of kGtRows x kGtCols (fks_gram_tiled.h)
 std::vector<GramPass> gram_tiled_passes(int krows, int kcols, bool symmetric);
 
@@ -403,6 +418,9 @@ void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const ui
 // fks_gram_mt_tiled: fks_gram_mt's matrix in passes of kGmtTile x kGmtTile seeds on the f64 matrix unit
 void gram_mt_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
                    int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_gram_mt_bs: the same matrix, the bf16 fast segments bit-sliced in passes of two 16-seed blocks
+void gram_mt_bs(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_expand_multi: nvec outputs written in place (outs[nvec][nt]), coefs[nvec][k], betas[nvec] or null
 int64_t expand_launch_work();  // kExpLaunchWork, or FKS_EXPAND_WORK where it is set to a positive number
 size_t expand_ws_bytes(const fks_tensor* t, int nt, int k, int nvec);

@@ -407,6 +407,56 @@ GramMtTiledWs gram_mt_tiled_ws(const fks_tensor* t, int nt, int shard, int nshar
   return w;
 }
 
+// fks_gram_mt_bs's passes.  A rectangular call tiles its cells by one 16-seed block each way, row
+// blocks outermost, every pass a pair pass.  A symmetric call walks the list in groups of
+// kGmbsPassSeeds seeds: the group's DIAGONAL pass (col0 == row0, up to 32 seeds: the tiles (0,0),
+// (0,1), (1,1) of its two blocks), then each of its row blocks against every column block of the
+// later groups, a pair pass each.  Every pair c >= r is computed once (the diagonal tiles whole)
+// and the reduce mirrors it.
+std::vector<GramPass> gram_mt_bs_passes(int krows, int kcols, bool symmetric) {
+  std::vector<GramPass> p;
+  if (!symmetric) {
+    for (int r0 = 0; r0 < krows; r0 += kGmtTile)
+      for (int c0 = 0; c0 < kcols; c0 += kGmtTile)
+        p.push_back(GramPass{r0, std::min(kGmtTile, krows - r0), c0, std::min(kGmtTile, kcols - c0)});
+    return p;
+  }
+  for (int g0 = 0; g0 < krows; g0 += kGmbsPassSeeds) {
+    const int ng = std::min(kGmbsPassSeeds, krows - g0);
+    p.push_back(GramPass{g0, ng, g0, ng});
+    for (int r0 = g0; r0 < g0 + ng; r0 += kGmtTile)
+      for (int c0 = g0 + kGmbsPassSeeds; c0 < krows; c0 += kGmtTile)
+        p.push_back(GramPass{r0, std::min(kGmtTile, g0 + ng - r0), c0, std::min(kGmtTile, krows - c0)});
+  }
+  return p;
+}
+
+// fks_gram_mt_bs's workspace: fks_gram_mt_tiled's whole layout (the tiles of a pass follow each
+// other on the stream, each reduced before the next takes the partial areas), then the windows of
+// one pass's seeds at every chunk start of the slice kernel's plan and that launch's partial
+// tiles, which stay until the pass's last tile is reduced.  The slice kernel's plan is the one plan_image
+// builds for the shard (the same chunk count and the same 2^31-word limit on a chunk pair); without
+// it the bf16 fast segments count among fks_gram_mt_tiled's launches.  Nothing depends on the seed
+// counts.  A request of its own: no existing call's layout or plan moves with it.
+GramMtBsWs gram_mt_bs_ws(const fks_tensor* t, int nt, int shard, int nshards, int cus) {
+  GramMtBsWs w;
+  w.one = gram_mt_tiled_ws(t, nt, shard, nshards, cus);
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  if (!L.segs[FKS_BF16].empty()) {
+    const std::vector<int64_t> bcb = chunk_table(br, bs_nchunks(br.hi - br.lo, cus));
+    const int n = (int)bcb.size() - 1;
+    w.bs_chunks = n;
+    for (int c = 0; c < n; c++)
+      if ((bcb[(size_t)std::min(c + 2, n)] - bcb[(size_t)c]) * kMtN >= ((int64_t)1 << 31)) w.bs_chunks = 0;
+  }
+  w.bs_states_off = align_up(w.one.total, 256);
+  w.bs_partial_off = w.bs_states_off + align_up(sizeof(uint32_t) * kMtN * (size_t)kGmbsPassSeeds * (size_t)w.bs_chunks, 256);
+  w.total = w.bs_partial_off + sizeof(double) * (size_t)(kGmbsDiagTiles * kGmtCells) * (size_t)std::max(w.bs_chunks, 1);
+  return w;
+}
+
 // fks_project_mt_bs's workspace: the per-call table of vector pieces in front, as
 // fks_project_mt_multi's, then the sink, ONE window area -- the bit-sliced launch's windows of a
 // pass of min(k, kBsPassSeeds) seeds at every chunk start of the slice kernel's plan, which the

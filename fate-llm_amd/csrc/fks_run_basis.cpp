@@ -770,6 +770,161 @@ void gram_mt_tiled(const fks_tensor* t, int nt, const uint64_t* rows, int kr, co
   }
 }
 
+// ---- bit-sliced seed-basis Gram matrix (CPU generator's stream) ----
+// A pass holds two blocks of kGmtTile seeds (fks_gram_mt_bs_passes): their windows are jumped to
+// EVERY chunk start of the slice kernel's plan -- a diagonal pass's seeds in one launch, a pair
+// pass's row block when the row block begins and its column block per pass -- and one
+// fks_gram_mt_bs_kernel launch over the bf16 fast segments leaves the pass's tile(s).  Everything
+// else -- the other dtypes' fast segments and the irregular work (and the bf16 fast segments of a
+// plan without the slice kernel's chunk table) -- goes through gram_mt_tiled's launches, one 16 x
+// 16 tile of the pass at a time over that call's window and partial areas, and the tile's reduce
+// adds the bit-sliced chunks in front of them.
+void gram_mt_bs(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
+                int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const bool symmetric = cols == nullptr;
+  if (symmetric) {
+    cols = rows;
+    kc = kr;
+  }
+  const DevCaps dc = device_caps();
+  GramMtBsWs W;
+  if (nt > 0) W = gram_mt_bs_ws(t, nt, shard, nshards, dc.cus);
+  if (!W.one.work) return zero_result(dev_out, (size_t)kr * (size_t)kc, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const bool bs = C->have_bs;  // the bf16 fast segments take the bit-sliced kernel
+  const int nbs = bs ? C->Z.bs_chunks : 0;
+  const int nirr = C->have_irr ? C->Z.irr_chunks : 0;
+  int nreg = 0;  // partial tiles of one tile's other fast launches
+  V.each_fast_dtype([&](int d, int, size_t) { nreg += bs && d == FKS_BF16 ? 0 : C->Z.reg_chunks; });
+  if (nbs + nreg + nirr < 1 || nbs > W.bs_chunks || nreg > W.one.reg_rows ||
+      (nreg && C->Z.reg_chunks > W.one.reg_chunks) || nirr > W.one.irr_chunks)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  // one seed's windows at the regular (irregular, slice plan's) chunk starts, in words
+  const size_t reg_win = (size_t)kMtN * (size_t)C->Z.reg_chunks, irr_win = (size_t)kMtN * (size_t)nirr;
+  const size_t bs_win = (size_t)kMtN * (size_t)nbs;
+  uint32_t* const reg_rows = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* const reg_cols = reg_rows + (size_t)kGmtTile * reg_win;
+  uint32_t* const irr_rows = reinterpret_cast<uint32_t*>(ws + W.one.irr_off);
+  uint32_t* const irr_cols = irr_rows + (size_t)kGmtTile * irr_win;
+  uint32_t* const sub = reinterpret_cast<uint32_t*>(ws + W.one.sub_off);
+  double* const partial = reinterpret_cast<double*>(ws + W.one.partial_off);
+  double* const irr_partial = reinterpret_cast<double*>(ws + W.one.irr_partial_off);
+  uint32_t* const bs_blk0 = reinterpret_cast<uint32_t*>(ws + W.bs_states_off);
+  uint32_t* const bs_blk1 = bs_blk0 + (size_t)kGmtTile * bs_win;
+  double* const bs_partial = reinterpret_cast<double*>(ws + W.bs_partial_off);
+  auto copy_windows = [&](uint32_t* dst, const uint32_t* src, int n) {
+    check_hip(hipMemcpyAsync(dst, src, sizeof(uint32_t) * irr_win * (size_t)n, hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream), "hipMemcpyAsync");
+  };
+  auto jump_bs = [&](const uint64_t* seeds, int n, uint32_t* states) {
+    JumpArgs ja = jump_args(seeds, n, static_cast<const uint8_t*>(C->dev), C->H.off_bs_polys, C->H.off_bs_cb, states, nbs);
+    ja.stride = 1;  // every plan chunk
+    ja.chunks_per_wg = std::max(1, std::min(n * nbs >= 4096 ? 32 : 16, nbs));
+    check_launch(timed(1, stream, [&] { return launch_jump(ja, n, stream); }), "fks_jump_kernel");
+  };
+  int tile_row0 = -1;  // the row block whose windows the regular and irregular areas hold
+  // one 16 x 16 tile: gram_mt_tiled's pass without the launches the bit-sliced kernel stands for,
+  // then the reduce over the bit-sliced launch's tile `bs_tile` (of `bs_tiles`) and their partials
+  auto tile = [&](int row0, int nr, int col0, int nc, int bs_tile, int bs_tiles) {
+    const bool diag = symmetric && col0 == row0;  // the column block holds the row block's seeds
+    if (nreg + nirr > 0 && row0 != tile_row0) {
+      tile_row0 = row0;
+      if (nreg) V.jump_regular(rows + row0, nr, reg_rows);
+      if (nirr) V.jump_irregular(rows + row0, nr, irr_rows);
+    }
+    if (nreg) {
+      if (!diag) V.jump_regular(cols + col0, nc, reg_cols);
+      double* out = partial;
+      V.each_fast_dtype([&](int d, int dd, size_t) {
+        if (bs && d == FKS_BF16) return;
+        GramMtTiledArgs ga{};
+        ga.row_states = reg_rows;
+        ga.col_states = diag ? nullptr : reg_cols;
+        ga.segs = V.at<DevSeg>(C->seg_off[d]);
+        ga.chunk_block = V.at<int64_t>(C->H.off_cb);
+        ga.partial = out;
+        ga.nsegs = C->nsegs[d];
+        ga.nchunks = C->Z.reg_chunks;
+        ga.nrows = nr;
+        ga.ncols = nc;
+        ga.diag = diag ? 1 : 0;
+        check_launch(timed(0, stream, [&] { return launch_gram_mt_tiled(dd, ga, stream); }),
+                     "fks_gram_mt_tiled_kernel", "bad arguments");
+        out += (size_t)kGmtCells * (size_t)C->Z.reg_chunks;
+      });
+    }
+    if (nirr) {
+      if (!diag) V.jump_irregular(cols + col0, nc, irr_cols);
+      const uint32_t* const col_src = diag ? irr_rows : irr_cols;
+      for (int m0 = 0; m0 < nr; m0 += kGramMtRows) {
+        const int mr = std::min(kGramMtRows, nr - m0);
+        copy_windows(sub, irr_rows + (size_t)m0 * irr_win, mr);
+        for (int n0 = 0; n0 < nc; n0 += kGramMtCols) {
+          const int mc = std::min(kGramMtCols, nc - n0);
+          copy_windows(sub + (size_t)mr * irr_win, col_src + (size_t)n0 * irr_win, mc);
+          GramMtIrrArgs ia{};
+          V.fill_irregular(ia, sub);
+          ia.partial = irr_partial + (size_t)kGmtIrrCells * (size_t)nirr *
+                                         (size_t)((m0 / kGramMtRows) * kGmtSubCols + n0 / kGramMtCols);
+          ia.nseeds = mr + mc;
+          ia.nrows = mr;
+          ia.ncols = mc;
+          check_launch(timed(0, stream, [&] { return launch_gram_mt_irr(ia, stream); }), "fks_gram_mt_irr_kernel",
+                       "bad arguments");
+        }
+      }
+    }
+    check_launch(launch_gram_mt_bs_reduce(bs_partial + (size_t)bs_tile * kGmtCells, nbs, (int64_t)bs_tiles * kGmtCells,
+                                          partial, nreg, irr_partial, nirr, nr, nc, dev_out, kc, row0, col0, symmetric,
+                                          stream),
+                 "fks_gram_mt_bs_reduce_kernel", "bad arguments");
+  };
+  int bs_row0 = -1;  // the row block whose windows bs_blk0 holds
+  for (const GramPass& p : gram_mt_bs_passes(kr, kc, symmetric)) {
+    const bool diag = symmetric && p.col0 == p.row0;  // up to kGmbsPassSeeds consecutive seeds
+    const int n0 = std::min<int>(p.nrows, kGmtTile), n1 = diag ? p.nrows - n0 : p.ncols;
+    if (bs) {
+      if (diag) {
+        jump_bs(rows + p.row0, p.nrows, bs_blk0);  // (bs_blk1 lies kGmtTile seeds behind bs_blk0)
+        bs_row0 = -1;
+      } else {
+        if (p.row0 != bs_row0) {  // a new row block: its windows, once
+          bs_row0 = p.row0;
+          jump_bs(rows + p.row0, n0, bs_blk0);
+        }
+        jump_bs(cols + p.col0, n1, bs_blk1);
+      }
+      GramMtBsArgs ba{};
+      ba.blk0 = bs_blk0;
+      ba.blk1 = bs_blk1;
+      ba.segs = V.at<DevSeg>(C->seg_off[FKS_BF16]);
+      ba.chunk_block = V.at<int64_t>(C->H.off_bs_cb);
+      ba.partial = bs_partial;
+      ba.nsegs = C->nsegs[FKS_BF16];
+      ba.nchunks = nbs;
+      ba.n0 = n0;
+      ba.n1 = n1;
+      ba.diag = diag ? 1 : 0;
+      check_launch(timed(0, stream, [&] { return launch_gram_mt_bs(ba, stream); }), "fks_gram_mt_bs_kernel",
+                   "bad arguments");
+    }
+    if (!diag) {
+      tile(p.row0, p.nrows, p.col0, p.ncols, 0, 1);
+    } else {
+      // the second block's diagonal tile first: the first block's windows then stay for the pair
+      // passes of its row block, which follow
+      if (n1) tile(p.row0 + kGmtTile, n1, p.col0 + kGmtTile, n1, 2, kGmbsDiagTiles);
+      tile(p.row0, n0, p.col0, n0, 0, kGmbsDiagTiles);
+      if (n1) tile(p.row0, n0, p.col0 + kGmtTile, n1, 1, kGmbsDiagTiles);
+    }
+  }
+}
+
 // ---- seed-basis expansion (CPU generator's stream) ----
 // project_mt_multi's frame run the other way: the geometry-only plan, the per-call table of the
 // outputs' pieces at the front of the workspace, then per output the passes of kMaxSeedsPerPass

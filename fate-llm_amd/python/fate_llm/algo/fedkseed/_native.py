@@ -41,6 +41,7 @@ EXPORTED = (
     "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
     "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes",
     "fks_gram_mt_tiled_workspace_size", "fks_gram_mt_tiled", "fks_gram_mt_tiled_passes",
+    "fks_gram_mt_bs_workspace_size", "fks_gram_mt_bs", "fks_gram_mt_bs_passes",
 )
 
 
@@ -156,6 +157,9 @@ def load():
         L.fks_gram_mt_tiled_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_gram_mt_tiled.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         L.fks_gram_mt_tiled_passes.argtypes = [c_i32, c_i32, c_i32, P, c_i32, ctypes.POINTER(c_i32)]
+        L.fks_gram_mt_bs_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_gram_mt_bs.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
+        L.fks_gram_mt_bs_passes.argtypes = [c_i32, c_i32, c_i32, P, c_i32, ctypes.POINTER(c_i32)]
         for name in ("fks_workspace_size", "fks_directional_step", "fks_perturb", "fks_normal",
                      "fks_host_jump_window", "fks_host_tables", "fks_directional_step_shard",
                      "fks_stream_length", "fks_profile_begin", "fks_profile_end", "fks_shard_census", "fks_perturb_step",
@@ -173,7 +177,8 @@ def load():
                      "fks_gram_workspace_size", "fks_gram", "fks_gram_passes",
                      "fks_gram_mt_workspace_size", "fks_gram_mt", "fks_gram_mt_passes",
                      "fks_gram_tiled_workspace_size", "fks_gram_tiled", "fks_gram_tiled_passes",
-                     "fks_gram_mt_tiled_workspace_size", "fks_gram_mt_tiled", "fks_gram_mt_tiled_passes"):
+                     "fks_gram_mt_tiled_workspace_size", "fks_gram_mt_tiled", "fks_gram_mt_tiled_passes",
+                     "fks_gram_mt_bs_workspace_size", "fks_gram_mt_bs", "fks_gram_mt_bs_passes"):
             getattr(L, name).restype = ctypes.c_int
         if L.fks_abi_version() != ABI_VERSION:
             raise OSError(f"libfks.so ABI {L.fks_abi_version()} != {ABI_VERSION}")

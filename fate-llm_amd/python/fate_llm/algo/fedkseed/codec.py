@@ -986,7 +986,7 @@ def gram_mt(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, sh
 
 
 def _gram_mt_call(specs, seeds, col_seeds, shard, nshards, call):
-    """gram_mt and gram_mt_tiled: the two C calls share their arguments (``call`` names one)."""
+    """gram_mt, gram_mt_tiled and gram_mt_bs: the C calls share their arguments (``call`` names one)."""
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     b = _Batch(list(specs), "torch_cpu", stage=False)  # the specs' data is not read: no staging copies
@@ -1024,6 +1024,23 @@ def gram_mt_tiled(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=No
     or number, the place in a tile or the passes --, and the matrix is exactly symmetric.  Draws
     nothing from torch's generators and leaves the codec's caches alone."""
     return _gram_mt_call(specs, seeds, col_seeds, shard, nshards, "fks_gram_mt_tiled")
+
+
+def gram_mt_bs(specs: Sequence[ParamSpec], seeds: Sequence[int], col_seeds=None, shard: int = 0,
+               nshards: int = 1) -> torch.Tensor:
+    """``gram_mt_tiled`` with the bf16 parameters' draws bit-sliced, 32 seeds per pass of the
+    generator (include/fks.h fks_gram_mt_bs): the same matrix on the torch_cpu stream, for large
+    seed counts over bf16 models.  A symmetric call draws 32 consecutive seeds at once and forms
+    their 528 pairs on the f64 matrix unit; its off-diagonal tiles and every rectangular call pair a
+    block of 16 row seeds with a block of 16 column seeds.  Arguments, shapes and checks are
+    ``gram_mt``'s.  Every product is exact and every addition f64, in the kernel's own fixed order
+    -- neither ``gram_mt``'s nor ``gram_mt_tiled``'s: it agrees with either to within
+    2 n 2^-52 sqrt(G_rr G_cc) over the n live elements, not bit for bit.  out[r, c] depends on the
+    device, the spec list, the shard and its two seeds only -- not on K, the other seeds, the pass
+    or bit plane a seed rode in, nor on whether the call was symmetric --, and the matrix is
+    exactly symmetric.  Specs that are not bf16 go through ``gram_mt_tiled``'s kernels.  Draws
+    nothing from torch's generators and leaves the codec's caches alone."""
+    return _gram_mt_call(specs, seeds, col_seeds, shard, nshards, "fks_gram_mt_bs")
 
 
 # outputs that share one pass of the generator in expand_multi (csrc/fks_expand.h kExpMaxVec;

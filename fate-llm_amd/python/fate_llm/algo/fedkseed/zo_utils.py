@@ -396,10 +396,11 @@ def _solve_normal_equations(G, b):
     return np.linalg.solve(low.T, y).T
 
 
-def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_stream, tiled=False):
+def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_stream, tiled=False, bitsliced=False):
     """fit_seed_scalars_exact (on_stream False: torch_rocm only),
-    fit_seed_scalars_exact_on_stream (True: either stream) and fit_seed_scalars_exact_tiled
-    (tiled True: torch_rocm only, G through codec.gram_tiled): the duplicate-seed check,
+    fit_seed_scalars_exact_on_stream (True: either stream), fit_seed_scalars_exact_tiled
+    (tiled True: torch_rocm only, G through codec.gram_tiled) and fit_seed_scalars_exact_bitsliced
+    (bitsliced True: torch_cpu's G through codec.gram_mt_bs): the duplicate-seed check,
     b = Z^T delta read in place, G = Z^T Z on the same stream, the host solve.  SYNCHRONISES: G
     and b are copied to the host."""
     seen = set()
@@ -418,7 +419,7 @@ def _fit_exact(name, param_groups, seeds, delta_vector_lists, stream_mode, on_st
                                   "either stream)")
     b = _project_in_place_on_stream(specs, seeds, vector_lists, stream_mode)
     if tiled and on_stream and mode == "torch_cpu":
-        G = codec.gram_mt_tiled(specs, seeds)
+        G = codec.gram_mt_bs(specs, seeds) if bitsliced else codec.gram_mt_tiled(specs, seeds)
     elif tiled:
         G = codec.gram_tiled(specs, seeds, stream_mode=stream_mode)
     else:
@@ -519,6 +520,42 @@ def fit_seed_scalars_exact_tiled_on_stream(param_groups: List[dict], seeds: Sequ
     differ from ``fit_seed_scalars_exact_on_stream``'s by the f64 summation order of G only."""
     return _fit_exact("fit_seed_scalars_exact_tiled_on_stream", param_groups, seeds, delta_vector_lists, stream_mode,
                       True, tiled=True)
+
+
+def _bitsliced_gram_stream(name, device, stream_mode):
+    """The bit-sliced Gram calls exist for the CPU generator's stream only."""
+    mode = codec.resolve_stream_mode(device, stream_mode)
+    if mode != "torch_cpu":
+        raise NotImplementedError(f"{name}: the bit-sliced Gram matrix is built for the torch_cpu stream only; "
+                                  f"this call resolves to the {mode} stream (seed_gram_tiled_on_stream and "
+                                  "fit_seed_scalars_exact_tiled_on_stream take either stream)")
+
+
+def seed_gram_bitsliced(param_groups: List[dict], seeds: Sequence[int], col_seeds=None, stream_mode=None) -> torch.Tensor:
+    """``seed_gram_tiled_on_stream``'s torch_cpu matrix through codec.gram_mt_bs: the bf16
+    parameters' draws bit-sliced, 32 seeds per pass of the generator, a symmetric call's 32
+    consecutive seeds paired among themselves in one pass.  G is exactly symmetric and
+    reproducible, and agrees with ``seed_gram_on_stream`` to within 2 n 2^-52 sqrt(G_rr G_cc), not
+    bit for bit.  torch_cpu stream only: a call that resolves to torch_rocm raises
+    NotImplementedError (``seed_gram_tiled_on_stream`` takes either stream)."""
+    params = [p for g in param_groups for p in g["params"]]
+    specs = [codec.ParamSpec(p.data, frozen=not p.requires_grad) for p in params]
+    _bitsliced_gram_stream("seed_gram_bitsliced", specs[0].tensor.device if specs else torch.device("cpu"), stream_mode)
+    return codec.gram_mt_bs(specs, seeds, col_seeds)
+
+
+def fit_seed_scalars_exact_bitsliced(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
+                                     stream_mode=None) -> torch.Tensor:
+    """``fit_seed_scalars_exact_tiled_on_stream`` on the torch_cpu stream with G from
+    codec.gram_mt_bs.  Arguments, result, errors and the synchronisation are
+    ``fit_seed_scalars_exact``'s; the scalars differ from ``fit_seed_scalars_exact_on_stream``'s by
+    the f64 summation order of G only.  torch_cpu stream only: a call that resolves to torch_rocm
+    raises NotImplementedError (``fit_seed_scalars_exact_tiled_on_stream`` takes either stream)."""
+    params = [p for g in param_groups for p in g["params"]]
+    _bitsliced_gram_stream("fit_seed_scalars_exact_bitsliced", params[0].device if params else torch.device("cpu"),
+                           stream_mode)
+    return _fit_exact("fit_seed_scalars_exact_bitsliced", param_groups, seeds, delta_vector_lists, stream_mode, True,
+                      tiled=True, bitsliced=True)
 
 
 def _expansion_outputs(params, outputs, m=None):

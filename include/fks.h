@@ -644,6 +644,46 @@ int fks_gram_mt_tiled(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds
                       void* workspace, size_t ws_bytes, void* stream);
 int fks_gram_mt_tiled_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
 
+/* ---- bit-sliced seed-basis Gram matrix on the CPU generator's stream (MT19937, f64 matrix unit) ----
+ * fks_gram_mt_bs: fks_gram_mt_tiled's matrix with the bf16 fast segments drawn by the slice
+ * kernel's bit-sliced generator, 32 seeds per generator state (fks_project_mt_bs's generator).
+ * Arguments, output shape, workspace rules and errors are fks_gram_mt_tiled's.  A pass holds two
+ * blocks of 16 seeds in the 32 planes of one state.  The PAIR form holds a row block and a column
+ * block and leaves their one 16 x 16 tile; rectangular calls and the off-diagonal tiles of a
+ * symmetric call use it.  The DIAGONAL form of a symmetric call holds 32 consecutive seeds of the
+ * list and leaves the tiles (0,0), (0,1) and (1,1): 528 pairs for 32 draws, so K = 64 is two
+ * diagonal and four pair passes where fks_gram_mt_tiled runs ten.  Everything that is not a bf16
+ * fast segment -- the f32 fast segments, all irregular work, and the bf16 fast segments of a plan
+ * without the slice kernel's chunk table -- goes through fks_gram_mt_tiled's launches, tile by
+ * tile of the pass.
+ * Contract: fks_gram_mt_tiled's sum, every product exact in f64 and every addition f64, in ONE
+ * fixed order of this call's own: over the bf16 fast segments the matrix unit's order over the
+ * four elements of one MFMA (element 16 g + 8 h + j of a 128-word task, j < 8, is slot j & 3 of
+ * step 4 g + 2 (j >> 2) + h), a wave's 32 steps per task, the tasks a wave takes of a plan chunk
+ * (task n goes to wave n mod 8) in order, the workgroup's eight waves in wave order; then, per
+ * cell, the slice plan's chunks in chunk order followed by fks_gram_mt_tiled's partials of the
+ * other launches, in 16 interleaved runs, then the runs in order.  It is neither fks_gram_mt's
+ * order nor fks_gram_mt_tiled's: within n 2^-52 sqrt(G_rr G_cc) of the true sum over the n live
+ * elements of the shard, so within 2 n 2^-52 sqrt(G_rr G_cc) of either, and not their bits.
+ * Reproducibility: an element depends on the device, the tensor list, the shard and its two
+ * seeds, and on nothing else -- not on K, the other seeds, the pass or bit plane a seed rode in,
+ * the form of the pass, nor whether the call was symmetric or rectangular.  Seeds past a block's
+ * count are not drawn and their cells are never written out.  <z_r, z_c> and <z_c, z_r> are the
+ * same products in the same order: the matrix is exactly symmetric.  dev_out is OVERWRITTEN in
+ * stream order, every element; an element written twice receives the same bits.
+ * Workspace: fks_gram_mt_bs_workspace_size (8-byte aligned; a function of the list and the
+ * device's CU count, whatever krows and kcols): fks_gram_mt_tiled's areas with the partials of a
+ * pass's three tiles, the windows of one pass's 32 seeds at the slice plan's chunk starts (a row
+ * block's are jumped once and kept while its column blocks pass) and that launch's partials.
+ * fks_gram_mt_bs_passes: the call's passes in launch order as (row0, nrows, col0, ncols); a
+ * symmetric call's pass with col0 == row0 is a diagonal pass of nrows == ncols <= 32 seeds, every
+ * other pass is a pair pass of at most 16 x 16 (host arithmetic only).                        */
+int fks_gram_mt_bs_workspace_size(const fks_tensor* t, int32_t nt, int32_t krows, int32_t kcols, size_t* bytes);
+int fks_gram_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* row_seeds, int32_t krows,
+                   const uint64_t* col_seeds, int32_t kcols, int32_t shard, int32_t nshards, double* dev_out,
+                   void* workspace, size_t ws_bytes, void* stream);
+int fks_gram_mt_bs_passes(int32_t krows, int32_t kcols, int32_t symmetric, int32_t* passes, int32_t cap, int32_t* n);
+
 /* ---- seed-basis expansion written in place (torch_rocm stream) ----
  * fks_expand_multi: the other direction of fks_project_multi, Z c instead of Z^T v: nvec dense
  * outputs, each written where it lies and in its own dtype.  outs is a HOST array of nvec x nt
