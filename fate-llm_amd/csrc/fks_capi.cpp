@@ -404,7 +404,7 @@ int fks_project_mt_multi_workspace_size(const fks_tensor* t, int32_t nt, int32_t
   });
 }
 
-// fks_project_mt_multi's argument checks, which fks_project_mt_bs shares
+// fks_project_mt_multi's argument checks, which fks_project_mt_bs and fks_project_mt_bs_tiled share
 static void project_mt_in_place_check(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k,
                                       const fks_vec* vecs, int32_t nvec, int32_t shard, int32_t nshards,
                                       const double* dev_out) {
@@ -463,6 +463,33 @@ int fks_project_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* seeds, in
     project_mt_bs_check_stream(t, nt);
     if (k == 0 || nvec == 0) return;
     project_mt_bs(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out, workspace, ws_bytes, stream);
+  });
+}
+
+// ... bit-sliced, kBsSeeds seeds by kPmbtVec vectors per pass
+static void project_mt_bs_tiled_check_stream(const fks_tensor* t, int nt) {
+  if (rocm_stream(t, nt))
+    throw Error(-FKS_ENOTSUP, "fks_project_mt_bs_tiled: the torch_rocm stream (FKS_STREAM_ROCM) is not supported here; "
+                              "fks_project_multi is the call for that stream");
+}
+
+int fks_project_mt_bs_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes) {
+  return guarded([&] {
+    validate(t, nt);
+    if (!bytes || k < 0 || nvec < 0) throw Error(-FKS_EINVAL, "bad arguments");
+    project_mt_bs_tiled_check_stream(t, nt);
+    *bytes = project_mt_bs_tiled_ws(t, nt, k, nvec, 0, 1, device_cu_count()).total;
+  });
+}
+
+int fks_project_mt_bs_tiled(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
+                            int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
+                            size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    project_mt_in_place_check(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out);
+    project_mt_bs_tiled_check_stream(t, nt);
+    if (k == 0 || nvec == 0) return;
+    project_mt_bs_tiled(t, nt, seeds, k, vecs, nvec, shard, nshards, dev_out, workspace, ws_bytes, stream);
   });
 }
 

@@ -12,6 +12,7 @@
 #include "fks_internal.h"
 #include "fks_project_mt.h"
 #include "fks_project_mt_bs.h"
+#include "fks_project_mt_bs_tiled.h"
 #include "fks_expand.h"
 #include "fks_expand_mt.h"
 #include "fks_expand_mt_bs.h"
@@ -143,6 +144,20 @@ struct ProjMtBsWs {
   size_t sub_stride = 0;   // doubles between two sub-passes' rows
 };
 ProjMtBsWs project_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
+// fks_project_mt_bs_tiled's: [vector table: nvec x entries pieces | sink 4 KB | windows of one 19-seed
+// sub-pass | windows of one pass of min(k, kBsSeeds) seeds at the slice plan's chunk starts, kept
+// while the pass's vector tiles go by | the bit-sliced launch's tiles [chunk][kPmbtVec][kBsSeeds] |
+// the sub-passes' rows [vector of the tile][sub][row][kPhxSeeds]]; offsets behind the table count
+// from inner_off
+struct ProjMtBsTiledWs {
+  ProjMtWs one;            // the 19-seed launches' bounds: work, entries, rows of one sub-pass
+  int bs_chunks = 0;       // chunks of the slice kernel's plan (0: no bf16 fast segment), at most
+  int subs = 0;            // 19-seed sub-passes of one pass, at most
+  int tile_vec = 0;        // vectors of one tile: min(nvec, kPmbtVec), at least 1
+  size_t inner_off = 0, bs_states_off = 0, bs_partial_off = 0, sub_partial_off = 0, total = 0;
+  size_t sub_stride = 0;   // doubles between two sub-passes' rows
+};
+ProjMtBsTiledWs project_mt_bs_tiled_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus);
 // fks_expand_mt_multi's, for one shard's plan: [output table: nvec x entries pieces | generator
 // windows of one pass | sink 4 KB | f32 staging area of one output].  The staging area exists for
 // k > kMaxSeedsPerPass only and holds the elements of the concatenation from the first to the last
@@ -412,6 +427,9 @@ void project_mt_multi(const fks_tensor* t, int nt, const uint64_t* seeds, int k,
 // fks_project_mt_bs: the same sums in passes of kBsPassSeeds seeds, the bf16 fast segments bit-sliced
 void project_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec, int shard,
                    int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
+// fks_project_mt_bs_tiled: passes of kBsSeeds seeds x kPmbtVec vectors, one draw for the tile's vectors
+void project_mt_bs_tiled(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
+                         int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);
 // fks_gram_mt: fks_gram on the CPU generator's stream, over the geometry-only plan
 void gram_mt(const fks_tensor* t, int nt, const uint64_t* rows, int kr, const uint64_t* cols, int kc, int shard,
              int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream);

@@ -481,6 +481,31 @@ ProjMtBsWs project_mt_bs_ws(const fks_tensor* t, int nt, int k, int nvec, int sh
   return w;
 }
 
+// fks_project_mt_bs_tiled's workspace: fks_project_mt_bs's order with TWO window areas -- the
+// 19-seed sub-passes' (one.partial_off: the sink and a 19-seed pass over the larger of its chunk
+// tables) and, behind it, the bit-sliced launch's windows of min(k, kBsSeeds) seeds at every chunk
+// start of the slice kernel's plan, which stay while the pass's vector tiles go by --, one tile of
+// sums per plan chunk and the rows of the sub-passes, each (vector of the tile, sub-pass) its own.
+// A request of its own: no existing call's layout or plan moves with it.
+ProjMtBsTiledWs project_mt_bs_tiled_ws(const fks_tensor* t, int nt, int k, int nvec, int shard, int nshards, int cus) {
+  ProjMtBsTiledWs w;
+  w.one = project_mt_ws(t, nt, k, shard, nshards, cus);
+  Layout L = make_layout(t, nt, nullptr, kProjMtGeoBase);
+  const BlockRange br = shard_blocks(L.stream_len, shard, nshards);
+  clip_segments(L, br);
+  if (!L.segs[FKS_BF16].empty()) w.bs_chunks = bs_nchunks(br.hi - br.lo, cus);
+  const int pass = std::max(1, std::min(k, kBsSeeds));
+  w.subs = (pass + kMaxSeedsPerPass - 1) / kMaxSeedsPerPass;
+  w.tile_vec = std::max(1, std::min(nvec, kPmbtVec));
+  w.inner_off = align_up(sizeof(ProjMtVecEntry) * (size_t)std::max(nvec, 0) * (size_t)w.one.entries, 256);
+  w.bs_states_off = w.one.partial_off;
+  w.bs_partial_off = w.bs_states_off + align_up(sizeof(uint32_t) * kMtN * (size_t)pass * (size_t)w.bs_chunks, 256);
+  w.sub_partial_off = w.bs_partial_off + sizeof(double) * (size_t)kPmbtCells * (size_t)std::max(w.bs_chunks, 1);
+  w.sub_stride = (size_t)kPhxSeeds * (size_t)std::max(w.one.rows, 1);
+  w.total = w.inner_off + w.sub_partial_off + sizeof(double) * w.sub_stride * (size_t)w.subs * (size_t)w.tile_vec;
+  return w;
+}
+
 // fks_expand_mt_bs's workspace: fks_expand_mt_multi's with one window area for both pass sequences
 // and the staging area wherever one of them runs a second pass.  The slice kernel's plan is the one
 // plan_image builds for the shard (the same chunk count and the same 2^31-word limit on a chunk

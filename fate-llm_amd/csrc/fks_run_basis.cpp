@@ -603,6 +603,136 @@ void project_mt_bs(const fks_tensor* t, int nt, const uint64_t* seeds, int k, co
   }
 }
 
+// ---- ... bit-sliced, in passes of kBsSeeds seeds by kPmbtVec vectors ----
+// project_mt_bs's plan and per-call table, one draw for the vectors of a tile.  A seed pass of at
+// most kBsSeeds seeds is one jump to EVERY chunk start of the slice kernel's plan, kept while the
+// vector tiles of that pass go by; a tile is one fks_project_mt_bs_tiled_kernel launch over the
+// bf16 fast segments.  Everything else -- the other dtypes' fast segments and the irregular work
+// (and the bf16 fast segments of a plan without the slice kernel's chunk table) -- goes through
+// project_mt_multi's one-vector launches in sub-passes of kMaxSeedsPerPass seeds: a sub-pass's
+// windows are jumped once per tile and serve the tile's vectors one after the other, each
+// (vector, sub-pass) with partial rows of its own.  One reduce per tile adds an entry's rows in
+// one order and overwrites it.  No window, z-index or reconstruct-window cache is read or written.
+void project_mt_bs_tiled(const fks_tensor* t, int nt, const uint64_t* seeds, int k, const fks_vec* vecs, int nvec,
+                         int shard, int nshards, double* dev_out, void* workspace, size_t ws_bytes, void* stream) {
+  const DevCaps dc = device_caps();
+  const ProjMtBsTiledWs W = project_mt_bs_tiled_ws(t, nt, k, nvec, shard, nshards, dc.cus);
+  if (!W.one.work) return zero_result(dev_out, (size_t)k * (size_t)nvec, stream);
+  require_workspace(workspace, ws_bytes, W.total);
+  thread_local std::vector<ProjMtVecEntry> host;  // the upload's source outlives the call
+  const MtVecTable T = mt_vec_table(host, t, nt, vecs, nvec, shard, nshards, W.one.entries);
+  const bool libm = libm_flavour(t, nt);
+  std::lock_guard<std::mutex> lk(g_cache_mu);  // no eviction while this call uses its entry
+  const CachedPlan* C = get_plan(t, nt, nullptr, kProjMtGeoBase, shard, nshards, /*small=*/false, dc);
+  const MtPlan V{*C, dc.cus, libm, stream};
+  const bool bs = C->have_bs;  // the bf16 fast segments take the bit-sliced kernel
+  const int nbs = bs ? C->Z.bs_chunks : 0;
+  // the rows of one sub-pass: the other dtypes' fast launches, then the irregular one
+  int rows = C->have_irr ? C->Z.irr_chunks : 0;
+  bool reg_rest = false;
+  size_t bf16_first = 0;
+  V.each_fast_dtype([&](int d, int, size_t first) {
+    if (bs && d == FKS_BF16) {
+      bf16_first = first;
+      return;
+    }
+    rows += C->Z.reg_chunks;
+    reg_rest = true;
+  });
+  if (!T.matches(*C) || nbs + rows < 1 || nbs > W.bs_chunks || rows > W.one.rows ||
+      ws_bytes_for(std::max(C->Z.reg_chunks, C->Z.irr_chunks), std::min(k, kMaxSeedsPerPass)) > W.one.partial_off)
+    throw Error(-FKS_EINVAL, kPlanMismatch);
+  check_hip(hipMemcpyAsync(workspace, host.data(), sizeof(ProjMtVecEntry) * host.size(), hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync");
+  const ProjMtVecEntry* table = static_cast<const ProjMtVecEntry*>(workspace);
+  const uint8_t* hdr = static_cast<const uint8_t*>(C->dev);
+  uint8_t* ws = static_cast<uint8_t*>(workspace) + W.inner_off;
+  const uint64_t* sink = reinterpret_cast<const uint64_t*>(ws);
+  uint32_t* states = reinterpret_cast<uint32_t*>(ws + kWsStatesOff);
+  uint32_t* const bs_states = reinterpret_cast<uint32_t*>(ws + W.bs_states_off);
+  double* const bs_partial = reinterpret_cast<double*>(ws + W.bs_partial_off);
+  double* const sub_partial = reinterpret_cast<double*>(ws + W.sub_partial_off);
+  const size_t vec_stride = W.sub_stride * (size_t)W.subs;  // doubles between two vectors' sub-pass rows
+  for (int s0 = 0; s0 < k; s0 += kBsSeeds) {
+    const int nb = std::min(kBsSeeds, k - s0);
+    const int64_t* bs_cb = nullptr;
+    if (bs) {  // the pass's windows, once
+      JumpArgs ja = jump_args(seeds + s0, nb, hdr, C->H.off_bs_polys, C->H.off_bs_cb, bs_states, nbs);
+      ja.stride = 1;  // every plan chunk
+      ja.chunks_per_wg = std::max(1, std::min(nb * nbs >= 4096 ? 32 : 16, nbs));
+      check_launch(timed(1, stream, [&] { return launch_jump(ja, nb, stream); }), "fks_jump_kernel");
+      bs_cb = ja.chunk_block;
+    }
+    for (int m0 = 0; m0 < nvec; m0 += kPmbtVec) {  // tiles of vectors over the same windows
+      const int nv = std::min(kPmbtVec, nvec - m0);
+      const ProjMtVecEntry* tab = table + (size_t)m0 * T.E;
+      if (bs) {
+        ProjMtBsTiledArgs ba{};
+        ba.states = bs_states;
+        ba.segs = V.at<DevSeg>(C->seg_off[FKS_BF16]);
+        ba.chunk_block = bs_cb;
+        ba.sink = sink;
+        ba.partial = bs_partial;
+        ba.pv = tab + bf16_first;
+        ba.pv_stride = (int64_t)T.E;
+        ba.nsegs = C->nsegs[FKS_BF16];
+        ba.nchunks = nbs;
+        ba.nseeds = nb;
+        ba.nvec = nv;
+        check_launch(timed(0, stream, [&] { return launch_project_mt_bs_tiled(ba, stream); }),
+                     "fks_project_mt_bs_tiled_kernel", "bad arguments");
+      }
+      for (int u0 = 0; u0 < nb && rows > 0; u0 += kMaxSeedsPerPass) {  // the 19-seed launches' sub-passes
+        const int nu = std::min(kMaxSeedsPerPass, nb - u0);
+        const uint64_t* const sub_seeds = seeds + s0 + u0;
+        // vector m's rows of this sub-pass; the fast launches' first
+        auto rows_of = [&](int m) { return sub_partial + vec_stride * (size_t)m + W.sub_stride * (size_t)(u0 / kMaxSeedsPerPass); };
+        size_t fast_rows = 0;
+        if (reg_rest) {
+          V.jump_regular(sub_seeds, nu, states);
+          for (int m = 0; m < nv; m++) {
+            double* row = rows_of(m);
+            V.each_fast_dtype([&](int d, int dd, size_t first) {
+              if (bs && d == FKS_BF16) return;
+              ProjMtMultiArgs pa{};
+              V.fill_fast(pa, d, states);
+              pa.sink = sink;
+              pa.partial = row;
+              pa.pv = tab + (size_t)m * T.E + first;
+              pa.stride = (int64_t)T.E;
+              pa.nseeds = nu;
+              pa.nvec = 1;
+              check_launch(timed(0, stream, [&] { return launch_project_mt_multi(dd, pa, stream); }),
+                           "fks_project_mt_multi_kernel", "bad arguments");
+              row += (size_t)kPhxSeeds * (size_t)C->Z.reg_chunks;
+            });
+            fast_rows = (size_t)(row - rows_of(m));
+          }
+        }
+        if (C->have_irr) {
+          V.jump_irregular(sub_seeds, nu, states);
+          for (int m = 0; m < nv; m++) {
+            ProjMtIrrMultiArgs ia{};
+            V.fill_irregular(ia, states);
+            ia.partial = rows_of(m) + fast_rows;
+            ia.rv = tab + (size_t)m * T.E + T.nsegs;
+            ia.tv = tab + (size_t)m * T.E + T.nsegs + T.nruns;
+            ia.stride = (int64_t)T.E;
+            ia.nseeds = nu;
+            ia.nvec = 1;
+            check_launch(timed(0, stream, [&] { return launch_project_mt_irr_multi(ia, stream); }),
+                         "fks_project_mt_irr_multi_kernel", "bad arguments");
+          }
+        }
+      }
+      check_launch(launch_project_mt_bs_tiled_reduce(bs_partial, nbs, sub_partial, rows, (int64_t)W.sub_stride,
+                                                     (int64_t)vec_stride, nb, nv,
+                                                     dev_out + (size_t)m0 * (size_t)k + s0, k, stream),
+                   "fks_project_mt_bs_tiled_reduce_kernel", "bad arguments");
+    }
+  }
+}
+
 // ---- seed-basis Gram matrix (CPU generator's stream) ----
 // gram's passes over project_mt_multi's geometry-only plan.  The windows of a pass lie in the
 // workspace as the kernels read them, the row tile's first and the column tile's behind them,

@@ -34,6 +34,7 @@ EXPORTED = (
     "fks_project_multi_workspace_size", "fks_project_multi", "fks_project_mt_workspace_size", "fks_project_mt",
     "fks_project_mt_multi_workspace_size", "fks_project_mt_multi",
     "fks_project_mt_bs_workspace_size", "fks_project_mt_bs",
+    "fks_project_mt_bs_tiled_workspace_size", "fks_project_mt_bs_tiled",
     "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
     "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
     "fks_expand_mt_bs_workspace_size", "fks_expand_mt_bs",
@@ -137,6 +138,8 @@ def load():
         L.fks_project_mt_multi.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         L.fks_project_mt_bs_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_project_mt_bs.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
+        L.fks_project_mt_bs_tiled_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
+        L.fks_project_mt_bs_tiled.argtypes = [P, c_i32, P, c_i32, P, c_i32, c_i32, c_i32, P, P, c_sz, P]
         L.fks_expand_multi_workspace_size.argtypes = [P, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]
         L.fks_expand_multi.argtypes = [P, c_i32, P, P, c_i32, P, P, c_i32, c_i32, c_i32, P, c_sz, P]
         L.fks_expand_launch_cuts.argtypes = [P, c_i32, c_i32, c_i32, c_i32, ctypes.c_int64, ctypes.c_int64, P, c_i32,
@@ -171,6 +174,7 @@ def load():
                      "fks_project_multi", "fks_project_mt_workspace_size", "fks_project_mt",
                      "fks_project_mt_multi_workspace_size", "fks_project_mt_multi",
                      "fks_project_mt_bs_workspace_size", "fks_project_mt_bs",
+                     "fks_project_mt_bs_tiled_workspace_size", "fks_project_mt_bs_tiled",
                      "fks_expand_multi_workspace_size", "fks_expand_multi", "fks_expand_launch_cuts",
                      "fks_expand_mt_multi_workspace_size", "fks_expand_mt_multi",
                      "fks_expand_mt_bs_workspace_size", "fks_expand_mt_bs",

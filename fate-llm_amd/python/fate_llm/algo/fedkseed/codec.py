@@ -783,8 +783,26 @@ def project_mt_bs(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, sha
                              bitsliced=True)
 
 
+def project_mt_bs_tiled(specs: Sequence[ParamSpec], seeds: Sequence[int], vectors, shard: int = 0,
+                        nshards: int = 1) -> torch.Tensor:
+    """``project_mt_bs``'s sums for many vectors (include/fks.h fks_project_mt_bs_tiled): the same
+    arguments, argument checks, staging and keep-alive, float64[M, K] on the specs' device.  One
+    bit-sliced draw of 32 seeds serves up to 16 vectors: over the bf16 specs' fast segments the z
+    and the vectors are the two operands of the f64 matrix unit, 32 seeds x 16 vectors per pass;
+    fp32 and fp16 specs and all irregular work take ``project_mt_multi``'s one-vector launches.
+    Every product is exact and the f64 additions run in this call's own fixed order: out[m, s] lies
+    within n 2^-52 sum |v z| of the exact sum and depends only on vectors[m]'s values, seeds[s], the
+    spec list, the shard and the device -- a call with K seeds and M vectors equals the K x M
+    one-seed, one-vector calls bit for bit -- but it is neither ``project_mt_bs``'s bits nor
+    ``project_mt_multi``'s.  Nothing routes to it.  Draws nothing from torch's generators and
+    leaves them and every attached cache alone."""
+    return _project_in_place(list(specs), seeds, [list(v) for v in vectors], "torch_cpu", shard, nshards,
+                             bitsliced="tiled")
+
+
 def _project_in_place(specs, seeds, vectors, mode, shard, nshards, bitsliced=False) -> torch.Tensor:
-    """project_multi (torch_rocm), project_mt_multi and project_mt_bs (torch_cpu) behind their stream checks."""
+    """project_multi (torch_rocm), project_mt_multi, project_mt_bs and project_mt_bs_tiled (torch_cpu: bitsliced
+    False, True, "tiled") behind their stream checks."""
     if nshards < 1 or not 0 <= shard < nshards:
         raise ValueError(f"shard {shard} of {nshards}")
     M, n = len(vectors), len(specs)
@@ -822,6 +840,7 @@ def _project_in_place(specs, seeds, vectors, mode, shard, nshards, bitsliced=Fal
         return out
     L = N.load()
     size_fn, fn = ((L.fks_project_multi_workspace_size, L.fks_project_multi) if mode == "torch_rocm" else
+                   (L.fks_project_mt_bs_tiled_workspace_size, L.fks_project_mt_bs_tiled) if bitsliced == "tiled" else
                    (L.fks_project_mt_bs_workspace_size, L.fks_project_mt_bs) if bitsliced else
                    (L.fks_project_mt_multi_workspace_size, L.fks_project_mt_multi))
     with torch.cuda.device(b.device):

@@ -355,6 +355,25 @@ def seed_projections_bitsliced(param_groups: List[dict], seeds: Sequence[int], v
     return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode)
 
 
+def seed_projections_bitsliced_tiled(param_groups: List[dict], seeds: Sequence[int], vector_lists=None,
+                                     stream_mode=None) -> torch.Tensor:
+    """``seed_projections_bitsliced`` for many vector lists, float64[M, K]: a call that resolves to
+    torch_cpu takes codec.project_mt_bs_tiled -- one bit-sliced draw of 32 seeds serves up to 16
+    lists on the f64 matrix unit --, one that resolves to torch_rocm codec.project_multi, as
+    ``seed_projections_bitsliced`` routes.  ``vector_lists`` and the default (one list, every
+    parameter's ``.grad``) are that function's.  On torch_cpu the sums have
+    codec.project_mt_bs_tiled's own fixed order: entry [m, s] equals the one-list, one-seed call bit
+    for bit and lies within n 2^-52 sum |v z| of the exact sum; it shares neither
+    ``seed_projections_bitsliced``'s bits nor ``seed_projections_in_place``'s.  torch's generators
+    are left alone."""
+    specs, vector_lists, _ = _projection_specs(param_groups, vector_lists)
+    if not specs:
+        return torch.zeros((len(vector_lists), len(seeds)), dtype=torch.float64)
+    if codec.resolve_stream_mode(specs[0].tensor.device, stream_mode) == "torch_cpu":
+        return codec.project_mt_bs_tiled(specs, seeds, vector_lists)
+    return codec.project_multi(specs, seeds, vector_lists, stream_mode=stream_mode)
+
+
 def fit_seed_scalars_in_place(param_groups: List[dict], seeds: Sequence[int], delta_vector_lists,
                               stream_mode=None) -> torch.Tensor:
     """``fit_seed_scalars_multi`` on either stream: ``seed_projections_in_place / N``,

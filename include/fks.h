@@ -544,6 +544,43 @@ int fks_project_mt_bs(const fks_tensor* t, int32_t nt, const uint64_t* seeds, in
                       int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* ---- ... bit-sliced, 32 seeds by 16 vectors per pass ----
+ * fks_project_mt_bs_tiled: fks_project_mt_bs's sums for many vectors, with a contract of its own.
+ * The arguments, the layout of vecs (a HOST array of nvec x nt fks_vec, any of the three dtypes,
+ * aligned to the element size only, NULL allowed for frozen or empty tensors) and of dev_out
+ * ([nvec][k] doubles), the shards, the empty cases and the errors are exactly fks_project_mt_bs's
+ * (argument errors: -FKS_EINVAL before any device work; a list that carries FKS_STREAM_ROCM:
+ * -FKS_ENOTSUP).  The bf16 fast segments run on the bit-sliced generator, ONE draw of 32 seeds
+ * serving up to 16 vectors: the z of a state's 32 seeds and the loaded vectors are the operands
+ * of v_mfma_f64_16x16x4_f64 (Z^T V, 32 seeds x 16 vectors per pass).  The f32 and f16 tensors and
+ * all irregular work run through fks_project_mt_multi's one-vector launches in sub-passes of 19
+ * seeds, as in fks_project_mt_bs.
+ *   - Value: dev_out[m * k + s] = sum over the shard's non-frozen elements e of
+ *     (double)f32(vec_m[e]) * (double)z_s(e), z_s what fks_normal writes for seeds[s] on this
+ *     stream.
+ *   - Arithmetic: every product is exact in f64 and every addition is f64, in ONE fixed order of
+ *     this call's own (the matrix unit's sums over a wave's tasks of a plan chunk in task order,
+ *     the waves in wave order, then per entry the slice plan's chunks in chunk order and the rows
+ *     of the 19-seed launches in fks_project_mt's row order, in 64 interleaved runs and the runs in
+ *     order; no floating-point atomic).  The result lies within n 2^-52 sum |v z| of the exact sum
+ *     (n the shard's elements).  It is NOT fks_project_mt_bs's bits and NOT fks_project_mt_multi's.
+ *   - Independence: dev_out[m * k + s] depends only on vector m's values, seeds[s], the list, the
+ *     shard and the device -- not on k or the seed's position, the bit plane or pass a seed rode
+ *     in, nvec, the vector's index or its column in the tile, the other vectors, the vector's dtype
+ *     beyond its values, or its alignment.  A call with k seeds and nvec vectors equals the
+ *     k x nvec one-seed, one-vector calls bit for bit.
+ *   - Side effects: dev_out is OVERWRITTEN in stream order.  Nothing is drawn from any generator
+ *     of the caller's, and no window, z-index or reconstruct-window cache is touched; the plan is
+ *     fks_project_mt_multi's geometry-only plan on the slice kernel's chunk table, and the table
+ *     of vector pieces travels at the front of the workspace, uploaded in stream order.
+ * Workspace: fks_project_mt_bs_tiled_workspace_size (8-byte aligned; a function of the list, k,
+ * nvec and the device's CU count alone; it grows with k up to 32 and with nvec up to 16 beyond the
+ * table).                                                                                     */
+int fks_project_mt_bs_tiled_workspace_size(const fks_tensor* t, int32_t nt, int32_t k, int32_t nvec, size_t* bytes);
+int fks_project_mt_bs_tiled(const fks_tensor* t, int32_t nt, const uint64_t* seeds, int32_t k, const fks_vec* vecs,
+                            int32_t nvec, int32_t shard, int32_t nshards, double* dev_out, void* workspace,
+                            size_t ws_bytes, void* stream);
+
 /* ---- seed-basis Gram matrix on the CPU generator's stream (MT19937) ----
  * fks_gram_mt: fks_gram's contract on fks_project_mt's stream.  dev_out[r * kc + c] = sum over
  * the non-frozen tensors i and the elements e that element shard `shard` of `nshards` owns of
